@@ -15,7 +15,17 @@ The headline config is BASELINE config 3 (1M x 4 KiB, zero-byte density sweep
 10/50/90 %): `value` is the p = 0.5 step; `sweep` times every density, each with
 its own encode/decode roofline fraction.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the
+round-trip check and the result line. --full adds every other measurement to the same line: the
+p = 0.1 / 0.9 legs of the density sweep, the HBM ceilings, the dense-stream, read-message, framing,
+RPC-framer, skewed-size (C5), validate and C1 legs, the PCIe-inclusive host path and the CPU
+baseline (each can be switched off with its --no-* option).
+
+--dump-outputs DIR writes what the last timed step left in the caller's buffers as
+DIR/<name>.npy (float32 / float64, under 64 MB in all; see dump_outputs). The inputs depend only
+on the arguments, so two builds run with the same arguments can be compared file by file.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
      --gpus N without a torchrun environment: this process starts N ranks (one per
      GPU, RCCL) as child processes before anything touches a GPU, and exits with
      their status; under torchrun (WORLD_SIZE set) each process is one rank.
@@ -57,6 +67,11 @@ def parse():
     ap.add_argument("--unit-bytes", type=int, default=4096)
     ap.add_argument("--zero-thresh", type=int, default=128, help="zero-byte probability x 256 (128 = 0.5)")
     ap.add_argument("--seed", type=int, default=0xC0DE0003)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the density sweep, the HBM ceilings, every side leg, the host path and the "
+                         "CPU baseline (the --no-* options below switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the p = 0.1 / 0.9 legs of the density sweep")
     ap.add_argument("--sweep", action="store_true", help=argparse.SUPPRESS)  # the sweep is the default now
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -73,7 +88,10 @@ def parse():
     ap.add_argument("--no-ceilings", action="store_true", help="skip the HBM ceiling sweep (headline-only traces)")
     ap.add_argument("--only", default="", help=argparse.SUPPRESS)  # dev: run one side leg (validate, c5, ...)
     ap.add_argument("--decoder", default="", help=argparse.SUPPRESS)  # dev: capnp_packed_set_decoder name
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Workload:
@@ -879,6 +897,55 @@ def validate_leg(args, dev, reps=10, n=1 << 20, distinct=4096, cpu_s=3.0):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # of the 64 MB a dump may take; the rest is slack for the .npy headers
+DUMP_MAX_LENGTHS = 1 << 20  # per-unit arrays are written whole up to this many units, sampled above
+
+
+def dump_outputs(wl, gathered, args, rank, world):
+    """Write what a caller of the timed path holds after the last timed step, as
+    DIR/<name>.npy (rank r > 0 of a multi-rank run: <name>_rank<r>.npy):
+      packed_len, unpacked_len (float64), encode_status, decode_status (float32): the per-unit
+        results of encode_batch / decode_batch, every unit (a seeded sample of 1M units, listed in
+        unit_index, when the batch has more);
+      packed_totals (float64): the all-gathered per-rank packed totals;
+      packed_bytes, unpacked_bytes (float32, one row per sampled unit): the unit's packed slot,
+        zero past its packed length (the encoder leaves that part of a slot unwritten), and its
+        decoded slot, for a seeded sample of units listed in sample_index (float64).
+    The samples depend only on --seed and the batch shape, so two runs with the same arguments
+    write the same units."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    n, ub, slot = wl.n, wl.ub, wl.slot
+    rng = np.random.default_rng(args.seed)
+    dev = wl.plen.device
+
+    def save(name, t, dtype):
+        np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), t.cpu().numpy().astype(dtype))
+
+    if n > DUMP_MAX_LENGTHS:
+        unit = torch.from_numpy(np.sort(rng.choice(n, DUMP_MAX_LENGTHS, replace=False))).to(dev)
+        save("unit_index", unit, np.float64)
+        pick = lambda t: t[unit]  # noqa: E731
+    else:
+        pick = lambda t: t  # noqa: E731
+    save("packed_len", pick(wl.plen), np.float64)
+    save("unpacked_len", pick(wl.ulen), np.float64)
+    save("encode_status", pick(wl.pst), np.float32)
+    save("decode_status", pick(wl.ust), np.float32)
+    save("packed_totals", gathered.reshape(-1), np.float64)
+    left = DUMP_BUDGET_BYTES - (24 if n <= DUMP_MAX_LENGTHS else 32) * min(n, DUMP_MAX_LENGTHS) - 8 * world
+    k = max(1, min(n, left // (4 * (slot + ub) + 8)))
+    # a unit too long for the budget (then k = 1) is cut to a prefix of its packed and decoded slots
+    cut = slot if 4 * (slot + ub) + 8 <= left else max(1, left // 8)
+    idx = torch.from_numpy(np.sort(rng.choice(n, k, replace=False))).to(dev)
+    pk = wl.d_pk.view(n, slot)[idx, :cut]
+    pk = pk * (torch.arange(cut, device=dev)[None, :] < wl.plen[idx][:, None])
+    save("sample_index", idx, np.float64)
+    save("packed_bytes", pk, np.float32)
+    save("unpacked_bytes", wl.d_out.view(n, ub)[idx, :min(ub, cut)], np.float32)
+
+
 def load_traffic(config_key):
     """PMC HBM bytes per launch for this config (scripts/pmc_traffic.py output)."""
     path = os.environ.get("CPK_TRAFFIC_JSON") or os.path.join(HERE, "profiles", "pmc_traffic.json")
@@ -1003,6 +1070,8 @@ def main():
     n, ub = args.units, args.unit_bytes
     wl = Workload(n, ub, args.seed, args.zero_thresh, unit_base=rank * n, dev=dev)
     head = measure(wl, args, args.steps, args.warmup, world, dev)
+    if args.dump_outputs:
+        dump_outputs(wl, head["gathered"], args, rank, world)
     ok_t = torch.tensor([1 if head["ok"] else 0], device="cpu" if _host_collectives() else dev)
     if world > 1:
         dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
@@ -1016,7 +1085,7 @@ def main():
                 "packed_ratio": round(m["P"] / (n * ub), 4), "bit_exact_roundtrip": m["ok"]}
 
     extra = {}
-    if world == 1:
+    if world == 1 and args.full:
         extra["sweep"] = {"p0.5": sweep_entry(head, args.zero_thresh, args.steps)}
         if not args.no_sweep:
             for thr, name in ((26, "p0.1"), (230, "p0.9")):
@@ -1104,9 +1173,9 @@ def main():
         if args.same_gpu and world > 1:
             line["same_gpu_rehearsal"] = {"ranks": world, "devices": 1, "collectives": "gloo",
                                           "note": "all ranks share cuda:0: checks the N-rank step, not a scaling number"}
-        if world == 1 and not args.no_host_path:
+        if world == 1 and args.full and not args.no_host_path:
             line["host_path"] = host_path(args, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

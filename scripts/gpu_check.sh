@@ -26,13 +26,13 @@ rc=$?; echo "pytest rc=$rc"; tail -15 "$OUT/pytest_gpu.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest crashed/hung: stopping"; exit $rc; fi
 
 echo "[gpu_check] $(date -u +%T) bench"
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 if [ $rc -ne 0 ]; then exit $rc; fi
 
 echo "[gpu_check] $(date -u +%T) rocprofv3 kernel trace"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-    python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+    python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
 rc=$?; echo "rocprof rc=$rc"; tail -3 "$OUT/prof.err"
 find "$OUT/prof" -name '*stats*' | head
 exit $rc
