@@ -175,6 +175,11 @@ SIGNATURES = {
     "capnp_packed_status_name": (ctypes.c_char_p, [ctypes.c_int]),
     "capnp_packed_encode_bound": (_sz, [_sz]),
     "capnp_packed_encode": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
+    "capnp_packed_encode_dialect": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_uint32]),
+    "capnp_packed_encode_batch_dialect": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                                         ctypes.c_uint32, _vp, _sz, _vp]),
+    "capnp_packed_encode_message_batch_dialect": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp,
+                                                                 _vp, _vp, ctypes.c_uint32, _vp]),
     "capnp_packed_decoded_size": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_decode": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_encode_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -225,6 +230,9 @@ SIGNATURES = {
 
 # capnp_packed_set_decoder values (include/capnp_packed.h)
 DECODERS = {"auto": 0, "twopass": 1, "fused": 2, "stream": 3, "words": 4}
+# encoder dialects (include/capnp_packed.h): "zig" = packPacked's bytes (the default everywhere),
+# "cxx" = the bytes of the C++ capnp packer and pycapnp (opt-in)
+DIALECTS = {"zig": 0, "cxx": 1}
 # capnp_packed_set_launch_flags bits (include/capnp_packed.h)
 LAUNCH_LONG_INLINE = 0x1
 LAUNCH_MID_SIDE_STREAM = 0x2
@@ -261,6 +269,13 @@ def _raise(st: int, what: str = ""):
     raise cls(f"{what}: {lib().capnp_packed_status_name(st).decode()} ({last_error()})")
 
 
+def _dialect(dialect) -> int:
+    try:
+        return DIALECTS[dialect]
+    except (KeyError, TypeError):
+        raise InvalidArgument(f"dialect must be 'zig' or 'cxx', not {dialect!r}") from None
+
+
 def _cbuf(data) -> ctypes.Array:
     b = bytes(data)
     return ctypes.create_string_buffer(b, max(1, len(b)))
@@ -274,13 +289,18 @@ def encode_bound(n: int) -> int:
     return lib().capnp_packed_encode_bound(n)
 
 
-def pack_packed(data) -> bytes:
-    """packPacked (message.zig:200-271). Raises InvalidMessageSize if len % 8."""
+def pack_packed(data, dialect="zig") -> bytes:
+    """packPacked (message.zig:200-271). Raises InvalidMessageSize if len % 8.
+    dialect="cxx": the C++ capnp packer's bytes of the buffer as one piece."""
+    d = _dialect(dialect)
     data = bytes(data)
     cap = encode_bound(len(data))
     out = ctypes.create_string_buffer(max(1, cap))
     n = _sz()
-    st = lib().capnp_packed_encode(_cbuf(data), len(data), out, cap, ctypes.byref(n))
+    if d == 0:
+        st = lib().capnp_packed_encode(_cbuf(data), len(data), out, cap, ctypes.byref(n))
+    else:
+        st = lib().capnp_packed_encode_dialect(_cbuf(data), len(data), out, cap, ctypes.byref(n), d)
     _raise(st, "packPacked")
     return out.raw[:n.value]
 
@@ -349,16 +369,21 @@ class MessageBuilder:
             self.create_segment()
         return frame_segments(self.segments)
 
-    def to_packed_bytes(self) -> bytes:
-        """message.zig:2175-2179: packPacked(toBytes())."""
-        return pack_packed(self.to_bytes())
+    def to_packed_bytes(self, dialect="zig") -> bytes:
+        """message.zig:2175-2179: packPacked(toBytes()). dialect="cxx": the bytes the C++
+        message writer gives these segments (table and segments packed piece by piece)."""
+        if _dialect(dialect) == 0:
+            return pack_packed(self.to_bytes())
+        if not self.segments:
+            self.create_segment()
+        return pack_message_cxx(self.segments)
 
     def write_to(self, writer) -> None:
         writer.write(self.to_bytes())
 
-    def write_packed_to(self, writer) -> None:
+    def write_packed_to(self, writer, dialect="zig") -> None:
         """message.zig:2209-2213."""
-        writer.write(self.to_packed_bytes())
+        writer.write(self.to_packed_bytes(dialect))
 
 
 class Message:
@@ -918,12 +943,21 @@ def _ws(ws):
     return (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
 
 
-def encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status, stream=None, ws=None) -> None:
+def encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status, stream=None, ws=None,
+                 dialect="zig") -> None:
     """Batch packPacked: unit i = d_in[in_off[i] : in_off[i]+in_len[i]] -> slot
     d_out[out_off[i] : out_off[i]+out_cap[i]]; out_len[i], status[i] per unit.
-    ws: optional workspace() tensor (capnp_packed_encode_batch_ws)."""
+    ws: optional workspace() tensor (capnp_packed_encode_batch_ws).
+    dialect="cxx": every unit as one piece under the C++ rule (capnp_packed_encode_batch_dialect)."""
+    d = _dialect(dialect)
     n = _units(in_off, in_len, out_off, out_cap, out_len, status)
-    if ws is None:
+    if d != 0:
+        if d_out is None:
+            raise InvalidArgument("encode_batch needs an output buffer (sizes only: encoded_size_batch)")
+        _raise(lib().capnp_packed_encode_batch_dialect(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out),
+                                                       _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
+                                                       d, *_ws(ws), _stream(stream)), "encode_batch_dialect")
+    elif ws is None:
         _raise(lib().capnp_packed_encode_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out),
                                                _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
                                                _stream(stream)), "encode_batch")
@@ -933,8 +967,14 @@ def encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status,
                                                   *_ws(ws), _stream(stream)), "encode_batch_ws")
 
 
-def encoded_size_batch(d_in, in_off, in_len, out_len, status, stream=None) -> None:
+def encoded_size_batch(d_in, in_off, in_len, out_len, status, stream=None, dialect="zig") -> None:
+    d = _dialect(dialect)
     n = _units(in_off, in_len, out_len, status)
+    if d != 0:
+        _raise(lib().capnp_packed_encode_batch_dialect(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, 0, 0, 0,
+                                                       _ptr(out_len), _ptr(status), d, 0, 0, _stream(stream)),
+               "encoded_size_batch_dialect")
+        return
     _raise(lib().capnp_packed_encoded_size_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(out_len),
                                                  _ptr(status), _stream(stream)), "encoded_size_batch")
 
@@ -972,17 +1012,52 @@ def read_message_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, c
 
 
 def encode_message_batch(seg_ptr, seg_len, seg_first, seg_count, d_out, out_off, out_cap, out_len, status,
-                         stream=None) -> None:
+                         stream=None, dialect="zig") -> None:
     """MessageBuilder.toPackedBytes (message.zig:2123-2179) for a batch of messages,
     packed straight from their segments. seg_ptr / seg_len: int64 tensors of segment
     device addresses and byte lengths; seg_first / seg_count: int32 tensors, one
-    entry per message. d_out None = packed sizes only."""
+    entry per message. d_out None = packed sizes only. dialect="cxx": the C++ message
+    writer's bytes (the segment table and each segment packed as pieces of their own)."""
+    d = _dialect(dialect)
     n = _units(seg_first, seg_count, out_len, status)
     if d_out is not None:
         _units(seg_first, out_off, out_cap)
+    if d != 0:
+        _raise(lib().capnp_packed_encode_message_batch_dialect(
+            _ptr(seg_ptr), _ptr(seg_len), _ptr(seg_first), _ptr(seg_count), n, _ptr(d_out), _ptr(out_off),
+            _ptr(out_cap), _ptr(out_len), _ptr(status), d, _stream(stream)), "encode_message_batch_dialect")
+        return
     _raise(lib().capnp_packed_encode_message_batch(_ptr(seg_ptr), _ptr(seg_len), _ptr(seg_first), _ptr(seg_count),
                                                    n, _ptr(d_out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
                                                    _ptr(status), _stream(stream)), "encode_message_batch")
+
+
+def pack_message_cxx(segments, device="cuda") -> bytes:
+    """One message's packed bytes under the C++ dialect, from host segments: they are
+    uploaded end to end and packed by encode_message_batch(dialect="cxx")."""
+    segs = [bytes(s) for s in segments] or [b""]
+    if len(segs) > MAX_SEGMENT_COUNT:
+        raise InvalidArgument(f"{len(segs)} segments (at most {MAX_SEGMENT_COUNT})")
+    for s in segs:
+        if len(s) % 8:
+            raise InvalidMessageSize("segment length is not a multiple of 8")
+    lens = np.array([len(s) for s in segs], dtype=np.int64)
+    total = int(lens.sum())
+    data = torch.from_numpy(np.frombuffer(b"".join(segs) + bytes(8), dtype=np.uint8).copy()).to(device)
+    offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+    seg_ptr = torch.from_numpy(offs + data.data_ptr()).to(device)
+    seg_len = torch.from_numpy(lens).to(device)
+    first = torch.zeros(1, dtype=torch.int32, device=device)
+    count = torch.full((1,), len(segs), dtype=torch.int32, device=device)
+    cap = encode_bound(8 * (len(segs) // 2 + 1) + total)
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    off = torch.zeros(1, dtype=torch.int64, device=device)
+    capt = torch.full((1,), cap, dtype=torch.int64, device=device)
+    ln = torch.zeros(1, dtype=torch.int64, device=device)
+    st = torch.full((1,), -1, dtype=torch.int32, device=device)
+    encode_message_batch(seg_ptr, seg_len, first, count, out, off, capt, ln, st, dialect="cxx")
+    _raise(int(st.item()), "toPackedBytes")
+    return out[:int(ln.item())].cpu().numpy().tobytes()
 
 
 def message_init_batch(d_in, in_off, in_len, max_segs, seg_count, seg_off, seg_len, status, stream=None) -> None:

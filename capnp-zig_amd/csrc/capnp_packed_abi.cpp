@@ -185,7 +185,7 @@ constexpr size_t kFastDecodeMax = 24 * 1024;  // packed bytes (the serial window
 constexpr size_t kFastEncodeMax = 4096;       // unpacked bytes: one 512-word tile
 
 int run_single(int kind, const uint8_t* in, size_t n, uint8_t* out, size_t slot, uint64_t* len_out,
-               uint64_t* used_out = nullptr, bool reuse_in = false) {
+               uint64_t* used_out = nullptr, bool reuse_in = false, uint32_t dialect = CAPNP_PACKED_DIALECT_ZIG) {
     int st = g_ctx.init();
     if (st) return st;
     if (n > SIZE_MAX - 16 || slot > SIZE_MAX - 16) return fail(CAPNP_PACKED_OUT_OF_SPACE, "buffer size overflows size_t");
@@ -216,6 +216,8 @@ int run_single(int kind, const uint8_t* in, size_t n, uint8_t* out, size_t slot,
     int32_t* d_status = reinterpret_cast<int32_t*>(m + 5);
     if (one && kind == 1)
         e = cpk::launch_decode_one(g_ctx.d_in, m, m + 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, s);
+    else if ((kind == 0 || kind == 3) && dialect == CAPNP_PACKED_DIALECT_CXX)
+        e = cpk::launch_encode_cxx(g_ctx.d_in, m, m + 1, 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, s);
     else if (one)
         e = cpk::launch_encode_one(g_ctx.d_in, m, m + 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, s);
     else if (kind == 0 || kind == 3)
@@ -304,6 +306,24 @@ int capnp_packed_encode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, s
     size_t bound = capnp_packed_encode_bound(n);
     uint64_t len = 0;
     st = run_single(0, in, n, out, cap < bound ? cap : bound, &len);
+    *out_len = (size_t)len;
+    return st;
+}
+
+int capnp_packed_encode_dialect(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
+                                uint32_t dialect) {
+    if (dialect == CAPNP_PACKED_DIALECT_ZIG) return capnp_packed_encode(in, n, out, cap, out_len);
+    if (dialect != CAPNP_PACKED_DIALECT_CXX) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
+    *out_len = 0;
+    if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
+    if (n % 8) return fail(CAPNP_PACKED_INVALID_MESSAGE_SIZE, "InvalidMessageSize");
+    int st = ensure_device();
+    if (st) return st;
+    std::lock_guard<std::mutex> lock(g_ctx.mu);
+    size_t bound = capnp_packed_encode_bound(n);
+    uint64_t len = 0;
+    st = run_single(0, in, n, out, cap < bound ? cap : bound, &len, nullptr, false, dialect);
     *out_len = (size_t)len;
     return st;
 }
@@ -420,6 +440,34 @@ int capnp_packed_encode_batch(const uint8_t* d_in, const uint64_t* d_in_off, con
                                         d_status, nullptr, 0, stream);
 }
 
+int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                      uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                      const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                      uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (dialect == CAPNP_PACKED_DIALECT_ZIG) {
+        if (d_out)
+            return capnp_packed_encode_batch_ws(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
+                                                d_status, d_workspace, workspace_bytes, stream);
+        // sizes only: capnp_packed_encoded_size_batch with the caller's workspace
+        int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
+        if (st || n == 0) return st;
+        if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;
+        hipError_t e = cpk::launch_encode(d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr, d_out_len, d_status,
+                                          false, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-size launch");
+    }
+    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
+    if (st || n == 0) return st;
+    const bool write = d_out != nullptr;
+    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
+    if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;  // checked, not used: one kernel
+    hipError_t e = cpk::launch_encode_cxx(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
+                                          d_status, write, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode launch");
+}
+
 int capnp_packed_encoded_size_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint64_t* d_out_len, int32_t* d_status, void* stream) {
     int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
@@ -503,6 +551,28 @@ int capnp_packed_encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t*
     if (st) return st;
     hipError_t e = cpk::launch_encode_message(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
                                               d_out_cap, d_out_len, d_status, write, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-message launch");
+}
+
+int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len,
+                                              const uint32_t* d_seg_first, const uint32_t* d_seg_count, uint32_t n,
+                                              uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                              uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
+                                              void* stream) {
+    if (dialect == CAPNP_PACKED_DIALECT_ZIG)
+        return capnp_packed_encode_message_batch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
+                                                 d_out_cap, d_out_len, d_status, stream);
+    if (dialect != CAPNP_PACKED_DIALECT_CXX) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (n == 0) return CAPNP_PACKED_OK;
+    if (!d_seg_first || !d_seg_count || !d_out_len || !d_status)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    const bool write = d_out != nullptr;
+    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
+    int st = ensure_device();
+    if (st) return st;
+    hipError_t e = cpk::launch_encode_message_cxx(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
+                                                  d_out_cap, d_out_len, d_status, write,
+                                                  static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-message launch");
 }
 

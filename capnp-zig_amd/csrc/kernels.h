@@ -71,6 +71,16 @@ hipError_t launch_encode_message(const uint64_t* seg_ptr, const uint64_t* seg_le
                                  const uint64_t* out_cap, uint64_t* out_len, int32_t* status, bool write,
                                  hipStream_t stream);
 
+// The C++ dialect (CAPNP_PACKED_DIALECT_CXX) of launch_encode / launch_encode_message: a wave per
+// unit / message in one kernel; no workspace, no side stream.
+hipError_t launch_encode_cxx(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                             uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
+                             int32_t* status, bool write, hipStream_t stream);
+hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* seg_len, const uint32_t* seg_first,
+                                     const uint32_t* seg_count, uint32_t n, uint8_t* out, const uint64_t* out_off,
+                                     const uint64_t* out_cap, uint64_t* out_len, int32_t* status, bool write,
+                                     hipStream_t stream);
+
 // Message.init segment-table parse (message.zig:341-394).
 hipError_t launch_message_init(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint32_t max_segs, uint32_t* seg_count, uint64_t* seg_off, uint64_t* seg_len,

@@ -1009,6 +1009,571 @@ __global__ __launch_bounds__(kBlock) void encode_tiled_kernel(const uint8_t* __r
     }  // queued units
 }
 
+constexpr uint32_t kMsgMaxSegs = 512;  // Message.max_segment_count (message.zig:310)
+
+// ---------------------------------------------------------------------------
+// ENCODE, C++ dialect (CAPNP_PACKED_DIALECT_CXX): the bytes the C++ capnp
+// packer and pycapnp write. Zero runs and tag records are the Zig rule's; a literal run opens
+// at a word without a zero byte (A) and goes on over words with at most ONE zero byte (A or
+// B), 255 at most, so a B word is 8 raw bytes inside an open run and a tag record outside one.
+// Which of the two is state, not a property of the word: encode_tile's
+// "head = ((i - run start) & 255) == 0" does not hold. Here the literal class is the A|B
+// stretch (a maximal run of A or B words); inside a stretch a run opens at the first A at or
+// after the stretch's origin and covers min(256, stretch end - head) words; a stretch that
+// goes on past the cap gets a new origin at head + 256 and the next run opens at the first A
+// from there (encode_tile_cxx resolves one link of that chain per round). Packing restarts
+// at every piece (a raw unit is one piece; a message's pieces are its segment table and each
+// segment), so no run state crosses a piece boundary.
+// ---------------------------------------------------------------------------
+
+// The rule one word after another; out == nullptr: the size only (pieces past the u32 word
+// index range only).
+__device__ uint64_t serial_pack_cxx(const uint8_t* in, uint64_t words, uint8_t* out) {
+    uint64_t o = 0, i = 0;
+    while (i < words) {
+        const uint64_t w = gload64(in + 8 * i);
+        const uint32_t tag = nonzero_tag(w);
+        if (tag == 0) {
+            uint64_t run = 1;
+            while (run < 256 && i + run < words && gload64(in + 8 * (i + run)) == 0) ++run;
+            if (out) { out[o] = 0; out[o + 1] = (uint8_t)(run - 1); }
+            o += 2;
+            i += run;
+            continue;
+        }
+        if (tag == 0xFF) {
+            uint64_t run = 1;
+            while (run < 256 && i + run < words && __popc(nonzero_tag(gload64(in + 8 * (i + run)))) >= 7) ++run;
+            if (out) {
+                out[o] = 0xFF;
+                for (int k = 0; k < 8; ++k) out[o + 1 + k] = (uint8_t)(w >> (8 * k));
+                out[o + 9] = (uint8_t)(run - 1);
+                for (uint64_t b = 0; b < 8 * (run - 1); ++b) out[o + 10 + b] = in[8 * (i + 1) + b];
+            }
+            o += 10 + 8 * (run - 1);
+            i += run;
+            continue;
+        }
+        uint32_t nz = 0;
+        for (int k = 0; k < 8; ++k) {
+            const uint8_t b = (uint8_t)(w >> (8 * k));
+            if (b) {
+                if (out) out[o + 1 + nz] = b;
+                ++nz;
+            }
+        }
+        if (out) out[o] = (uint8_t)tag;
+        o += 1 + nz;
+        i += 1;
+    }
+    return o;
+}
+
+// encode_lookahead for the C++ dialect: the first Z break and the first stretch break (a
+// word with two or more zero bytes) among words [0, nw) of src, nw <= 256.
+__device__ __forceinline__ void encode_lookahead_cxx(const uint8_t* src, uint32_t nw, uint32_t lane, uint32_t& bz,
+                                                     uint32_t& bs) {
+    uint32_t fz = nw, fs = nw;
+#pragma unroll
+    for (int t = 3; t >= 0; --t) {
+        const uint32_t i = 4 * lane + t;
+        if (i < nw) {
+            const uint32_t tg = nonzero_tag(*reinterpret_cast<const uint64_t*>(src + 8 * i));
+            if (tg != 0) fz = i;
+            if (__popc(tg) < 7) fs = i;
+        }
+    }
+    bz = wave_min(fz);
+    bs = wave_min(fs);
+}
+
+// The lane's words of a staged tile (lane j owns words [8j, 8j + 8) of `words`).
+__device__ __forceinline__ void tile_words_lds(uint64_t (&w)[8], const uint8_t* lds, uint32_t lane, uint32_t words) {
+    if (lane * 8 < words) {
+        const uint4* row = reinterpret_cast<const uint4*>(lds + lane * kEncRow);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint4 r = row[q];
+            w[2 * q] = (uint64_t)r.x | ((uint64_t)r.y << 32);
+            w[2 * q + 1] = (uint64_t)r.z | ((uint64_t)r.w << 32);
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) w[t] = 0;
+    }
+}
+// The same of a full 16-B aligned tile, straight from memory.
+__device__ __forceinline__ void tile_words_direct(uint64_t (&w)[8], const uint8_t* tile, uint32_t lane) {
+    const uint4* row = reinterpret_cast<const uint4*>(tile + 64 * lane);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint4 r = row[q];
+        w[2 * q] = (uint64_t)r.x | ((uint64_t)r.y << 32);
+        w[2 * q + 1] = (uint64_t)r.z | ((uint64_t)r.w << 32);
+    }
+}
+
+// encode_tile under the C++ rule: the tile is words [tb, tb + words) of a piece, w the lane's
+// eight of them (tile_words_lds / tile_words_direct). single (wave-uniform): the tile is
+// the whole piece, and the scans are skipped when no zero run and no stretch crosses a lane
+// boundary. Carries: cz_c as encode_tile's; ch_c the head (+ 1; 0: none) of the literal run
+// still open at the tile start. nbz / nbs: the first Z / stretch break at or after the tile
+// end. Per-word values (origins, run ends, sizes, counts) are derived from the lane's class
+// masks where they are used, not kept in arrays (95 VGPRs in the one-tile kernel, not 123).
+template <bool WRITE>
+__device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t* lut, uint32_t lane, uint32_t words,
+                                                    uint32_t tb, bool single, uint32_t& cz_c, uint32_t& ch_c,
+                                                    uint32_t nbz, uint32_t nbs, uint8_t* dst, uint64_t room,
+                                                    const uint64_t (&w)[8]) {
+    const uint32_t wend = tb + words;
+    const uint32_t base = tb + lane * 8;
+    const uint32_t nw = lane * 8 < words ? min(8u, words - lane * 8) : 0u;
+
+    uint32_t tagp[2] = {0, 0};                 // the 8 tags, a byte each
+    uint32_t zmask = 0, amask = 0, smask = 0;  // bit t: word t is all-zero / A / A or B
+    const uint32_t vmask = (1u << nw) - 1u;    // the lane's words inside the tile
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const uint32_t tg = nonzero_tag(w[t]);
+        tagp[t >> 2] |= tg << (8 * (t & 3));
+        zmask |= (tg == 0) ? 1u << t : 0u;
+        amask |= (tg == 0xFF) ? 1u << t : 0u;
+        smask |= (__popc(tg) >= 7) ? 1u << t : 0u;
+    }
+    zmask &= vmask;
+    amask &= vmask;
+    smask &= vmask;
+    auto tag_of = [&](int t) { return (tagp[t >> 2] >> (8 * (t & 3))) & 0xFFu; };
+    const uint32_t zb = ~zmask & vmask, sb = ~smask & vmask;  // the lane's Z breaks / stretch breaks
+    // last break + 1 and first break of the zero class (seeded with the carry / lookahead) and of
+    // the stretches (lbs 0: none in this lane), and the lane's last A (+ 1)
+    const uint32_t lbz = zb ? max(cz_c, base + 32u - __clz(zb)) : cz_c;
+    const uint32_t fbz = zb ? base + __ffs(zb) - 1u : nbz;
+    const uint32_t lbs = sb ? base + 32u - __clz(sb) : 0u;
+    const uint32_t fbs = sb ? base + __ffs(sb) - 1u : nbs;
+    const uint32_t la = amask ? base + 32u - __clz(amask) : 0u;
+    bool scan_z = true, scan_s = true;  // a zero run / a stretch crosses a lane boundary
+    if (single) {
+        const uint64_t bz0 = __ballot(zmask & 1u), bz7 = __ballot((zmask >> 7) & 1u);
+        const uint64_t bs0 = __ballot(smask & 1u), bs7 = __ballot((smask >> 7) & 1u);
+        scan_z = (bz0 & (bz7 << 1)) != 0;
+        scan_s = (bs0 & (bs7 << 1)) != 0;
+    }
+    // cz: zero-run start carried into the lane; oi: origin of the stretch that enters the lane
+    // (the carried head's position when a run is open at the tile start, so that run's words
+    // find it; else the tile start); pa: the nearest A before the lane (+ 1); ez / es: the
+    // first Z / stretch break after the lane
+    uint32_t cz = base, oi = base, pa = 0, ez = min(base + 8, wend), es = ez, lz_all = 0;
+    if (scan_z) {
+        const uint32_t mz = wave_incl_max(lbz, lane);
+        cz = wave_prev_lane(mz, 0u);
+        ez = next_break(fbz != nbz, fbz, lane, nbz);
+        if (lane == 0) cz = cz_c;
+        lz_all = readlane(mz, 63);
+    }
+    if (scan_s) {
+        const uint32_t csx = wave_prev_lane(wave_incl_max(lbs, lane), 0u);
+        oi = csx ? csx : (ch_c ? ch_c - 1 : tb);
+        pa = max(wave_prev_lane(wave_incl_max(la, lane), 0u), ch_c);
+        es = next_break(fbs != nbs, fbs, lane, nbs);
+    }
+
+    uint32_t zhead = zmask & ~(zmask << 1);  // bit t: word t heads a zero run (runs inside the lane)
+    if (scan_z) {
+        zhead = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t i = base + t;
+            zhead |= (((zmask >> t) & 1u) && ((i - cz) & 255u) == 0) ? 1u << t : 0u;
+            if (!((zmask >> t) & 1u)) cz = i + 1;
+        }
+    }
+
+    // Literal runs, one link of every stretch's chain per round. All unresolved words of a
+    // stretch share its origin: oi for the stretch that enters the lane, the word after the
+    // last break for one that starts in it. A round's heads are the unresolved A words with no
+    // A between the origin and themselves; a prefix max gives every word the last such head at
+    // or before it (run, + 1). A head at or after the origin covers the word when it is less
+    // than 256 words back; past that the origin moves to head + 256 and the word waits for the
+    // next round (only the entering stretch can: the others start less than 8 words back); no
+    // head at or after the origin: a B word outside any run (a tag record). A round moves every
+    // open origin on by at least 256 words and the carried run reaches the tile: three rounds.
+    uint32_t lhead = 0, lbody = 0, hd7 = 0;  // run heads, later words of runs, word 7's head (+ 1)
+    uint32_t unres = smask, seed = ch_c;
+    if (!scan_s) {
+        // every stretch lies inside its lane: a run is the words from a stretch's first A to its
+        // end. Flood the A bits upwards through the stretch bits (distance 1, 2, 4).
+        uint32_t c = amask, m = smask & (smask << 1);
+        c |= (c << 1) & smask;
+        c |= (c << 2) & m;
+        m &= m << 2;
+        c |= (c << 4) & m;
+        lhead = c & ~(c << 1);
+        lbody = c & ~lhead;
+        unres = 0;
+    }
+    for (int round = 0; scan_s && round < 4; ++round) {
+        if (__builtin_amdgcn_ballot_w64(unres != 0) == 0) break;  // wave-uniform
+        uint32_t hm = 0, lh = 0, org = oi, par = pa;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t i = base + t;
+            const bool h = (((unres & amask) >> t) & 1u) && par <= org;
+            hm |= h ? 1u << t : 0u;
+            lh = h ? i + 1 : lh;
+            org = ((smask >> t) & 1u) ? org : i + 1;
+            par = ((amask >> t) & 1u) ? i + 1 : par;
+        }
+        uint32_t run = max(seed, wave_prev_lane(wave_incl_max(lh, lane), 0u));
+        seed = 0;
+        org = oi;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t i = base + t, bit = 1u << t;
+            const bool u = (unres >> t) & 1u;
+            run = (u && ((hm >> t) & 1u)) ? i + 1 : run;
+            const bool found = run > org;              // a head at or after the origin
+            const bool near = found && i + 1 - run < 256u;
+            const bool wait = u && found && !near;     // beyond that run's 256 words
+            lhead |= (u && near && run == i + 1) ? bit : 0u;
+            lbody |= (u && near && run != i + 1) ? bit : 0u;
+            if (t == 7) hd7 = (u && near) ? run : hd7;
+            oi = wait ? run + 255u : oi;
+            unres = wait ? unres : unres & ~bit;
+            org = ((smask >> t) & 1u) ? org : i + 1;
+        }
+    }
+    uint32_t ch_out = 0;  // the run open at the end of a full tile
+    if (!single) {
+        const bool open = hd7 != 0 && hd7 + 255u > wend;
+        ch_out = readlane(open ? hd7 : 0u, 63);
+        if (words != kEncMaxWords) ch_out = 0;
+    }
+
+    // record sizes, a nibble each: 00: 2 bytes at a head; a run's head 10, its later words 8;
+    // else 1 + popc
+    uint32_t szp = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const uint32_t bit = 1u << t;
+        const uint32_t s = (zmask & bit) ? ((zhead & bit) ? 2u : 0u)
+                           : (lhead & bit) ? 10u : (lbody & bit) ? 8u : 1u + __popc(tag_of(t));
+        szp |= ((vmask & bit) ? s : 0u) << (4 * t);
+    }
+    auto size_of = [&](int t) { return (szp >> (4 * t)) & 15u; };
+    const uint32_t sz2 = (szp & 0x0F0F0F0Fu) + ((szp >> 4) & 0x0F0F0F0Fu);  // four sums of two, <= 20 each
+    const uint32_t total = (sz2 * 0x01010101u) >> 24;
+    const uint32_t incl = wave_incl_sum(total, lane);
+    const uint32_t P = readlane(incl, 63);
+    const uint32_t ob = incl - total;
+    cz_c = lz_all;
+    ch_c = ch_out;
+    if (!WRITE || (uint64_t)P > room) return P;
+
+    // ---- assemble in LDS and write back, as encode_tile ----------------------------------
+    const uint32_t so = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15);
+    const uint32_t nch_out = (so + P + 15) >> 4;
+    wave_lds_sync();  // every lane has its words in registers
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        uint32_t c = lane + 64 * k;
+        if (c < nch_out) *reinterpret_cast<uint4*>(lds + 16 * c) = make_uint4(0, 0, 0, 0);
+    }
+    wave_lds_sync();
+    {
+        // a head's count: min(256, class run end - i) - 1, the run end being the word's class's
+        // next break in the lane, or the first one after the lane
+        auto count_of = [&](int t, bool zt) {
+            const uint32_t after = (zt ? zb : sb) & ~((2u << t) - 1u);
+            const uint32_t e = after ? base + __ffs(after) - 1u : (zt ? ez : es);
+            return min(256u, e - (base + t)) - 1u;
+        };
+        const uint32_t x0 = so + ob;
+        uint32_t x = x0, ex = 0;  // ex bit t: a head whose count byte opens a third u64
+        if (nw != 0)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t tg = tag_of(t), sz = size_of(t);
+            uint64_t sel = lut[tg];
+            asm volatile("" : "+v"(sel));
+            const uint64_t rec = (uint64_t)tg | perm64(w[t], sel);
+            const bool zt = (zmask >> t) & 1u, head = (lhead >> t) & 1u, body = (lbody >> t) & 1u;
+            const uint32_t cnt = count_of(t, zt);
+            uint64_t lo = rec | ((uint64_t)(zt ? cnt : 0u) << 8);  // 00 <count>
+            lo = body ? w[t] : lo;                                 // a run's later word, raw (A or B)
+            lo = sz ? lo : 0ull;
+            const uint64_t hi = head ? ((w[t] >> 56) | ((uint64_t)cnt << 8)) : 0ull;
+            const uint32_t a = x & ~7u, sh = (x & 7u) * 8u;
+            atomicOr(reinterpret_cast<unsigned long long*>(lds + a), (unsigned long long)(lo << sh));
+            atomicOr(reinterpret_cast<unsigned long long*>(lds + a + 8),
+                     (unsigned long long)(((lo >> 1) >> (63u - sh)) | (hi << sh)));
+            ex |= (sh == 56 && (hi >> 8)) ? 1u << t : 0u;
+            x += sz;
+        }
+        if (__builtin_amdgcn_ballot_w64(ex != 0) != 0) {
+            x = x0;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                if ((ex >> t) & 1u)
+                    atomicOr(reinterpret_cast<unsigned long long*>(lds + (x & ~7u) + 16),
+                             (unsigned long long)(((w[t] >> 56) | ((uint64_t)count_of(t, false) << 8)) >> 8));
+                x += size_of(t);
+            }
+        }
+    }
+    wave_lds_sync();
+    {
+        uint8_t* gdst = dst - so;  // 16-B aligned
+        const uint32_t lo = so, hi = so + P;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            uint32_t c = lane + 64 * k;
+            if (c < nch_out) {
+                uint32_t cb = 16 * c, ce = cb + 16;
+                if (cb >= lo && ce <= hi) {
+                    __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(lds + cb),
+                                                reinterpret_cast<u32x4*>(gdst + cb));
+                } else {
+                    const uint32_t a = max(cb, lo), e = min(ce, hi);
+                    store_partial16(gdst + cb, a - cb, e - cb, *reinterpret_cast<const uint64_t*>(lds + cb),
+                                    *reinterpret_cast<const uint64_t*>(lds + cb + 8));
+                }
+            }
+        }
+    }
+    return P;
+}
+
+// One piece (words of src, 8-aligned, at most 0xFFFFF000), tile by tile as encode_tiled_kernel
+// walks a unit; its packed bytes go to dst + pos while they fit in cap.
+template <bool WRITE>
+__device__ __forceinline__ void encode_piece_cxx(uint8_t* lds, const uint64_t* lut, uint32_t lane, const uint8_t* src,
+                                                 uint32_t words, uint8_t* dst, uint64_t cap, uint64_t& pos,
+                                                 bool& fits) {
+    uint32_t cz = 0, ch = 0;
+    const bool single = words <= kEncMaxWords;
+    for (uint32_t tb = 0; tb < words; tb += kEncMaxWords) {
+        uint32_t lane_u = lane;
+        asm volatile("" : "+v"(lane_u));
+        const uint32_t tw = min(kEncMaxWords, words - tb);
+        const uint32_t te = tb + tw;
+        const uint8_t* const tsrc = src + 8ull * tb;
+        // a full 16-B aligned tile: the lane's 64 B straight from memory, no staging
+        const bool direct = tw == kEncMaxWords && !(reinterpret_cast<uintptr_t>(tsrc) & 15);
+        uint4 v[5];
+        uint64_t w[8];
+        if (direct) tile_words_direct(w, tsrc, lane_u);
+        else encode_load(v, tsrc, tw, lane_u);
+        uint32_t nbz = words, nbs = words;
+        if (te < words) {
+            const uint32_t la = min(256u, words - te);
+            uint32_t bz, bs;
+            encode_lookahead_cxx(src + 8ull * te, la, lane_u, bz, bs);
+            nbz = bz < la ? te + bz : (la == 256u ? te + 256u : words);
+            nbs = bs < la ? te + bs : (la == 256u ? te + 256u : words);
+        }
+        if (!direct) {
+            wave_lds_sync();  // the previous tile's write-back read the slice
+            encode_put(lds, v, (uint32_t)(reinterpret_cast<uintptr_t>(tsrc) & 15), tw, lane_u);
+            wave_lds_sync();
+            tile_words_lds(w, lds, lane_u, tw);
+        }
+        const uint64_t room = (WRITE && fits && pos <= cap) ? cap - pos : 0;
+        const uint32_t Pt = encode_tile_cxx<WRITE>(lds, lut, lane_u, tw, tb, single, cz, ch, nbz, nbs, dst + pos, room, w);
+        if ((uint64_t)Pt > room) fits = false;
+        pos += Pt;
+    }
+}
+
+// The units encode_cxx_long_kernel owns: valid word streams of more than one tile.
+// encode_cxx_kernel leaves exactly these alone (encode_kernel / encode_tiled_kernel's split: the
+// one-tile kernel keeps its register budget without the tile loop).
+__device__ __forceinline__ bool encode_cxx_long_unit(const uint8_t* in, uint64_t off, uint64_t len) {
+    return !(reinterpret_cast<uintptr_t>(in + off) & 7) && !(len & 7) && (len >> 3) > kEncMaxWords;
+}
+
+// A wave per unit of the batch: every unit of at most one tile (units of at most 64 words too:
+// DESIGN.md §2.9) and the statuses of invalid ones.
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void encode_cxx_kernel(const uint8_t* __restrict__ in,
+                                                            const uint64_t* __restrict__ in_off,
+                                                            const uint64_t* __restrict__ in_len, uint32_t n,
+                                                            uint8_t* __restrict__ out,
+                                                            const uint64_t* __restrict__ out_off,
+                                                            const uint64_t* __restrict__ out_cap,
+                                                            uint64_t* __restrict__ out_len,
+                                                            int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint32_t unit = blockIdx.x * kWavesPerBlock + wave;
+    const bool live = unit < n;  // wave-uniform
+    const uint64_t b0 = live ? in_off[unit] : 0ull, nbytes = live ? in_len[unit] : 0ull;
+    const uint8_t* const src = in + b0;
+    const bool valid = live && !(reinterpret_cast<uintptr_t>(src) & 7) && !(nbytes & 7);
+    const uint32_t words = valid && (nbytes >> 3) <= kEncMaxWords ? (uint32_t)(nbytes >> 3) : 0u;
+    // a full 16-B aligned tile (every unit of the headline): the lane's 64 B straight from memory,
+    // in flight while the block builds its selector table; else staged through LDS
+    const bool direct = words == kEncMaxWords && !(reinterpret_cast<uintptr_t>(src) & 15);
+    uint64_t w[8];
+    if (direct) tile_words_direct(w, src, lane);
+    else if (words) encode_stage(lds, src, words, lane);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    }
+    if (!live) return;
+    if (!valid) {
+        if (lane == 0) { out_len[unit] = 0; status[unit] = (reinterpret_cast<uintptr_t>(src) & 7) ? ST_ARG : ST_SIZE; }
+        return;
+    }
+    if ((nbytes >> 3) > kEncMaxWords) return;  // encode_cxx_long_kernel's
+    uint64_t ob = 0, cap = 0;
+    if (WRITE) {
+        ob = out_off[unit];
+        cap = out_cap[unit];
+    }
+    if (!direct) {
+        wave_lds_sync();
+        tile_words_lds(w, lds, lane, words);
+    }
+    uint32_t cz = 0, ch = 0;
+    const uint32_t P = encode_tile_cxx<WRITE>(lds, lut, lane, words, 0, true, cz, ch, words, words, out + ob, cap, w);
+    if (lane == 0) {
+        out_len[unit] = P;
+        status[unit] = (WRITE && (uint64_t)P > cap) ? ST_SPACE : ST_OK;
+    }
+}
+
+// The units of more than one tile (encode_cxx_long_unit), found by a small grid that strides
+// over the batch's lengths, 64 per load, and coded a wave each, tile by tile.
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void encode_cxx_long_kernel(const uint8_t* __restrict__ in,
+                                                                 const uint64_t* __restrict__ in_off,
+                                                                 const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                 uint8_t* __restrict__ out,
+                                                                 const uint64_t* __restrict__ out_off,
+                                                                 const uint64_t* __restrict__ out_cap,
+                                                                 uint64_t* __restrict__ out_len,
+                                                                 int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    }
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kWave;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kWave; ubase < n; ubase += stride) {
+        const uint64_t u = ubase + lane;
+        uint64_t todo = __ballot(u < n && encode_cxx_long_unit(in, in_off[u < n ? u : 0], in_len[u < n ? u : 0]));
+        while (todo) {  // wave-uniform
+            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint8_t* const src = in + in_off[unit];
+            const uint64_t nwords = in_len[unit] >> 3;
+            uint64_t ob = 0, cap = 0;
+            if (WRITE) {
+                ob = out_off[unit];
+                cap = out_cap[unit];
+            }
+            uint64_t pos = 0;
+            bool fits = true;
+            if (nwords > 0xFFFFF000ull) {  // word indices are u32: one lane
+                if (lane == 0) {
+                    pos = serial_pack_cxx(src, nwords, nullptr);
+                    if (WRITE) {
+                        fits = pos <= cap;
+                        if (fits) serial_pack_cxx(src, nwords, out + ob);
+                    }
+                }
+            } else {
+                encode_piece_cxx<WRITE>(lds, lut, lane, src, (uint32_t)nwords, out + ob, cap, pos, fits);
+            }
+            if (lane == 0) {
+                out_len[unit] = pos;
+                status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+            }
+        }
+    }
+}
+
+// MessageBuilder.toPackedBytes under the C++ dialect, a wave per message: the segment table
+// (built in the tile's LDS rows) is the first piece, then every segment in order.
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void encode_message_cxx_kernel(const uint64_t* __restrict__ seg_ptr,
+                                                                    const uint64_t* __restrict__ seg_len,
+                                                                    const uint32_t* __restrict__ seg_first,
+                                                                    const uint32_t* __restrict__ seg_count, uint32_t n,
+                                                                    uint8_t* __restrict__ out,
+                                                                    const uint64_t* __restrict__ out_off,
+                                                                    const uint64_t* __restrict__ out_cap,
+                                                                    uint64_t* __restrict__ out_len,
+                                                                    int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    }
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint32_t msg = blockIdx.x * kWavesPerBlock + wave;
+    if (msg >= n) return;  // wave-uniform
+    const uint32_t c_in = seg_count[msg];
+    const uint32_t first = seg_first[msg];
+    const uint32_t count = c_in == 0 ? 1u : c_in;  // at least one (empty) segment
+    if (count > kMsgMaxSegs) {
+        if (lane == 0) { out_len[msg] = 0; status[msg] = ST_ARG; }
+        return;
+    }
+    // the table's u32 entries (count - 1, the segments' words, padding) as words of the tile:
+    // entry k is half k & 1 of word k >> 1
+    const uint32_t hw = count / 2 + 1;
+    bool bad = false;
+    for (uint32_t k = lane; k < 2 * hw; k += kWave) {
+        uint32_t e = 0;
+        if (k == 0) e = count - 1;
+        else if (k <= count && c_in) {
+            const uint64_t len = seg_len[first + k - 1], ptr = seg_ptr[first + k - 1];
+            bad |= (len & 7) != 0 || (ptr & 7) != 0 || (len >> 3) > 0xFFFFF000ull;
+            e = (uint32_t)(len >> 3);
+        }
+        *reinterpret_cast<uint32_t*>(lds + (k >> 4) * kEncRow + ((k >> 1) & 7u) * 8 + (k & 1u) * 4) = e;
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        if (lane == 0) { out_len[msg] = 0; status[msg] = ST_ARG; }
+        return;
+    }
+    uint64_t ob = 0, cap = 0;
+    if (WRITE) {
+        ob = out_off[msg];
+        cap = out_cap[msg];
+    }
+    wave_lds_sync();
+    uint32_t cz = 0, ch = 0;
+    uint64_t wt[8];
+    tile_words_lds(wt, lds, lane, hw);
+    uint64_t pos = encode_tile_cxx<WRITE>(lds, lut, lane, hw, 0, true, cz, ch, hw, hw, out + ob, cap, wt);
+    bool fits = !WRITE || pos <= cap;
+    if (c_in) {
+        for (uint32_t s = 0; s < count; ++s) {  // wave-uniform
+            const uint64_t len = seg_len[first + s];
+            const uint8_t* const src = reinterpret_cast<const uint8_t*>(seg_ptr[first + s]);
+            encode_piece_cxx<WRITE>(lds, lut, lane, src, (uint32_t)(len >> 3), out + ob, cap, pos, fits);
+        }
+    }
+    if (lane == 0) {
+        out_len[msg] = pos;
+        status[msg] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // ENCODE straight from segment lists: MessageBuilder.toPackedBytes
 // (message.zig:2175-2179 = packPacked(toBytes()), toBytes 2123-2170) without the
@@ -1018,7 +1583,6 @@ __global__ __launch_bounds__(kBlock) void encode_tiled_kernel(const uint8_t* __r
 // lane gathers its 8 words of a tile from the header or from the segment that
 // holds them (word offsets of the segments in LDS).
 // ---------------------------------------------------------------------------
-constexpr uint32_t kMsgMaxSegs = 512;  // Message.max_segment_count (message.zig:310)
 constexpr uint32_t kMsgOneSegs = 64;   // one-tile pass: a segment per lane (more: the tiled pass)
 
 
@@ -6010,6 +6574,44 @@ hipError_t launch_encode_one(const uint8_t* in, const uint64_t* in_off, const ui
     else
         encode_kernel<false><<<1, kBlock, 0, stream>>>(in, in_off, in_len, 1, out, out_off, out_cap, out_len, status,
                                                          nullptr, nullptr);
+    return hipGetLastError();
+}
+
+// The C++ dialect's encoders: a wave per unit (one-tile units, then the longer
+// ones) / per message; no class pass, no side stream and no workspace.
+hipError_t launch_encode_cxx(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                             uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
+                             int32_t* status, bool write, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
+    // the units of more than one tile: a grid striding over the lengths, 64 per wave and load
+    const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
+    if (write) {
+        encode_cxx_kernel<true><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                               status);
+        encode_cxx_long_kernel<true><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                         out_len, status);
+    } else {
+        encode_cxx_kernel<false><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                                status);
+        encode_cxx_long_kernel<false><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off,
+                                                                          out_cap, out_len, status);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* seg_len, const uint32_t* seg_first,
+                                     const uint32_t* seg_count, uint32_t n, uint8_t* out, const uint64_t* out_off,
+                                     const uint64_t* out_cap, uint64_t* out_len, int32_t* status, bool write,
+                                     hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (write)
+        encode_message_cxx_kernel<true><<<blocks, kBlock, 0, stream>>>(seg_ptr, seg_len, seg_first, seg_count, n, out,
+                                                                       out_off, out_cap, out_len, status);
+    else
+        encode_message_cxx_kernel<false><<<blocks, kBlock, 0, stream>>>(seg_ptr, seg_len, seg_first, seg_count, n, out,
+                                                                        out_off, out_cap, out_len, status);
     return hipGetLastError();
 }
 

@@ -9,7 +9,9 @@
  *
  * Signatures use plain pointers, sizes and an opaque stream handle only.
  *
- * Codec rules are the Zig rules (NOT canonical C++ capnp): see DESIGN.md §1.
+ * Codec rules are the Zig rules by default (NOT canonical C++ capnp): see DESIGN.md §1. The
+ * capnp_packed_encode_*_dialect calls write the C++ capnp / pycapnp bytes on request
+ * (CAPNP_PACKED_DIALECT_CXX); every decoder reads both.
  *
  * Ownership: the caller owns every buffer. Output capacity is passed in; the
  * library never allocates caller-visible memory. A Zig caller allocates
@@ -41,7 +43,10 @@ extern "C" {
  *     capnp_packed_stream_contexts, CAPNP_PACKED_DECODER_WORDS; CAPNP_PACKED_DECODER_FUSED /
  *     _STREAM answer INVALID_ARGUMENT (those decoders were removed from the library in round 5,
  *     source at 869fccf), and the CPK_DECODE environment variable is gone
- *     (capnp_packed_set_decoder is the only selector). Round 6 changed no signature. */
+ *     (capnp_packed_set_decoder is the only selector). Round 6 changed no signature.
+ *   2, additions only: CAPNP_PACKED_DIALECT_ZIG / _CXX and capnp_packed_encode_dialect,
+ *     capnp_packed_encode_batch_dialect, capnp_packed_encode_message_batch_dialect (the opt-in
+ *     C++-canonical encoder). Nothing that existed changed. */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -317,6 +322,49 @@ int capnp_packed_encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t*
                                       const uint32_t* d_seg_first, const uint32_t* d_seg_count, uint32_t n,
                                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                       uint64_t* d_out_len, int32_t* d_status, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Encoder dialect: which packed bytes an encode call writes. An argument of the call (no
+ * process-wide setting: it changes the bytes, and threads may use both at once).
+ *   CAPNP_PACKED_DIALECT_ZIG  packPacked's bytes (message.zig:200-271): what every call
+ *                             without a dialect argument writes. A literal run (tag FF) goes
+ *                             on only over words without a zero byte.
+ *   CAPNP_PACKED_DIALECT_CXX  the bytes of the C++ capnp packer (capnp convert binary:packed)
+ *                             and pycapnp: a literal run opens at a word without a zero byte
+ *                             and goes on over words with at most one zero byte; and packing
+ *                             restarts at every piece the C++ message writer writes (a
+ *                             message's segment table, then each segment), so no run crosses
+ *                             from one piece to the next. A raw buffer is one piece. Never
+ *                             larger than the Zig bytes; every decoder here reads both.
+ * Any other value: INVALID_ARGUMENT, before any device work. With DIALECT_ZIG the calls
+ * forward to capnp_packed_encode / _encode_batch_ws / _encoded_size_batch /
+ * _encode_message_batch. Contracts (alignment, statuses, OUT_OF_SPACE, asynchrony, capture)
+ * are those calls'. The C++ dialect runs one kernel, a wave per unit or message: it needs no
+ * workspace (one passed is checked as the _ws calls check it, and not used) and never
+ * allocates; units of at most 64 words have no lane-per-unit kernel yet.
+ * ------------------------------------------------------------------------ */
+#define CAPNP_PACKED_DIALECT_ZIG 0u /* message.zig:200-271, what every existing call emits */
+#define CAPNP_PACKED_DIALECT_CXX 1u /* C++ capnp / pycapnp bytes */
+
+/* capnp_packed_encode with a dialect. */
+int capnp_packed_encode_dialect(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
+                                uint32_t dialect);
+
+/* capnp_packed_encode_batch_ws with a dialect; d_out == NULL computes the packed sizes only
+ * (capnp_packed_encoded_size_batch; d_out_off and d_out_cap may then be NULL). */
+int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                      uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                      const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                      uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* capnp_packed_encode_message_batch with a dialect. Under DIALECT_CXX message i's bytes are the
+ * packed segment table (8 * ceil((1 + count) / 2) bytes unpacked) followed by each packed
+ * segment, every piece packed on its own. */
+int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len,
+                                              const uint32_t* d_seg_first, const uint32_t* d_seg_count, uint32_t n,
+                                              uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                              uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
+                                              void* stream);
 
 /* Message.init (message.zig:341-394) segment-table parse of n framed messages
  * d_in[d_in_off[i] .. + d_in_len[i]) (e.g. the output of a decode batch).

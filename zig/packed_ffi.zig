@@ -49,6 +49,11 @@ extern "capnp_packed" fn capnp_packed_abi_version() u32;
 extern "capnp_packed" fn capnp_packed_last_error() [*:0]const u8;
 extern "capnp_packed" fn capnp_packed_encode_bound(n: usize) usize;
 extern "capnp_packed" fn capnp_packed_encode(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize) c_int;
+// Encoder dialect (include/capnp_packed.h): an argument of the call. dialect_zig is what every
+// call without the argument writes; dialect_cxx gives the C++ capnp / pycapnp bytes.
+pub const dialect_zig: u32 = 0;
+pub const dialect_cxx: u32 = 1;
+extern "capnp_packed" fn capnp_packed_encode_dialect(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize, dialect: u32) c_int;
 extern "capnp_packed" fn capnp_packed_decoded_size(in: [*]const u8, n: usize, out_size: *usize) c_int;
 extern "capnp_packed" fn capnp_packed_decode(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize) c_int;
 extern "capnp_packed" fn capnp_packed_read_message(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize, consumed: *usize) c_int;
@@ -109,6 +114,13 @@ pub extern "capnp_packed" fn capnp_packed_encode_message_batch(
     n: u32, d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64,
     d_out_len: [*]u64, d_status: [*]i32, stream: ?*anyopaque,
 ) c_int;
+/// capnp_packed_encode_message_batch with a dialect (dialect_cxx: the segment table and each
+/// segment packed as pieces of their own, the C++ message writer's bytes).
+pub extern "capnp_packed" fn capnp_packed_encode_message_batch_dialect(
+    d_seg_ptr: [*]const u64, d_seg_len: [*]const u64, d_seg_first: [*]const u32, d_seg_count: [*]const u32,
+    n: u32, d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64,
+    d_out_len: [*]u64, d_status: [*]i32, dialect: u32, stream: ?*anyopaque,
+) c_int;
 /// Message.init segment-table parse (message.zig:341-394) of n framed messages.
 pub extern "capnp_packed" fn capnp_packed_message_init_batch(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32, max_segs: u32,
@@ -135,6 +147,12 @@ pub extern "capnp_packed" fn capnp_packed_encode_batch_ws(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
     d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u64,
     d_out_len: [*]u64, d_status: [*]i32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
+) c_int;
+/// capnp_packed_encode_batch_ws with a dialect; d_out null: the packed sizes only.
+pub extern "capnp_packed" fn capnp_packed_encode_batch_dialect(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64,
+    d_out_len: [*]u64, d_status: [*]i32, dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
 ) c_int;
 pub extern "capnp_packed" fn capnp_packed_decode_batch_ws(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
@@ -256,6 +274,17 @@ pub fn packPacked(allocator: std.mem.Allocator, bytes: []const u8) Error![]u8 {
     errdefer allocator.free(buf);
     var len: usize = 0;
     try check(capnp_packed_encode(bytes.ptr, bytes.len, buf.ptr, buf.len, &len));
+    return allocator.realloc(buf, len);
+}
+
+/// packPacked with the C++ capnp packer's bytes (`bytes` as one piece): for files kept beside
+/// ones `capnp convert binary:packed` or pycapnp wrote. Every unpackPacked reads them.
+pub fn packPackedCxx(allocator: std.mem.Allocator, bytes: []const u8) Error![]u8 {
+    if (bytes.len % 8 != 0) return error.InvalidMessageSize;
+    const buf = try allocator.alloc(u8, capnp_packed_encode_bound(bytes.len));
+    errdefer allocator.free(buf);
+    var len: usize = 0;
+    try check(capnp_packed_encode_dialect(bytes.ptr, bytes.len, buf.ptr, buf.len, &len, dialect_cxx));
     return allocator.realloc(buf, len);
 }
 
