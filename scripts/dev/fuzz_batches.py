@@ -5,7 +5,12 @@ budget. Each round builds a batch of mixed units (small / mid / long sizes, dens
 (some too small), checks every status and byte against oracle.pack_batch, then decodes the
 packed units (some truncated or corrupted, some slots short) under auto / twopass / words and
 checks statuses, lengths and bytes against oracle.unpack_batch. Prints one JSON line.
-Usage: python3 scripts/dev/fuzz_batches.py [--seconds 240] [--units 20000]"""
+--read: the read-message leg instead. Each round draws the reader-stream corpus of a fresh seed
+(tests/reader_streams.py: ~6,000 streams around the framed-length cut), reads it in one
+read_message_batch launch in shuffled order and checks every unit against
+oracle_read_packed_message through the comparison of tests/test_gpu_read_message_fuzz.py; the
+summary counts the units per outcome class.
+Usage: python3 scripts/dev/fuzz_batches.py [--seconds 240] [--units 20000] [--read]"""
 import argparse
 import json
 import os
@@ -149,20 +154,41 @@ def one_round(rng, n, stats):
     return bad
 
 
+def read_round(rng, seed, stats):
+    """One corpus of reader streams through read_message_batch, against the oracle."""
+    import reader_streams as rs
+    from test_gpu_read_message_fuzz import read_and_compare, report
+    cases = rs.cases(seed)
+    cs = [cases[i] for i in rng.permutation(len(cases))]
+    bad, _, _ = read_and_compare(rng, cs, first_cap=int(rng.integers(0, 4)))
+    for c in cs:
+        route = "hdr" if c.fw is None else ("words" if c.fw <= rs.WORDS_ROUTE_MAX else "walk")
+        key = f"{route}:{rs.outcome(c) or c.status.lower()}"
+        stats["read_classes"][key] = stats["read_classes"].get(key, 0) + 1
+    stats["read_units"] += len(cs)
+    return [("read", seed) + r for r in report(cs, bad)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240)
     ap.add_argument("--units", type=int, default=20000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--big", action="store_true", help="add units of 64-256 KiB")
+    ap.add_argument("--read", action="store_true", help="the read-message leg (reader-stream corpora)")
     a = ap.parse_args()
     global BIG
     BIG = a.big
     rng = np.random.default_rng(a.seed)
     stats = {"rounds": 0, "enc_units": 0, "dec_units": 0}
+    if a.read:
+        stats = {"rounds": 0, "read_units": 0, "read_classes": {}}
     bad, t0 = [], time.time()
     while time.time() - t0 < a.seconds:
-        bad += one_round(rng, a.units, stats)
+        if a.read:
+            bad += read_round(rng, a.seed * 1000003 + stats["rounds"], stats)
+        else:
+            bad += one_round(rng, a.units, stats)
         stats["rounds"] += 1
         print(json.dumps({"progress": stats, "bad": len(bad), "t": round(time.time() - t0, 1)}), flush=True)
         if len(bad) > 50:
