@@ -180,6 +180,10 @@ SIGNATURES = {
                                                          ctypes.c_uint32, _vp, _sz, _vp]),
     "capnp_packed_encode_message_batch_dialect": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp,
                                                                  _vp, _vp, ctypes.c_uint32, _vp]),
+    "capnp_packed_encode_dense_workspace_bytes": (_sz, [ctypes.c_uint32]),
+    "capnp_packed_encode_dense_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64,
+                                                       ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _sz,
+                                                       _vp]),
     "capnp_packed_decoded_size": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_decode": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_encode_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -965,6 +969,34 @@ def encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status,
         _raise(lib().capnp_packed_encode_batch_ws(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out),
                                                   _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
                                                   *_ws(ws), _stream(stream)), "encode_batch_ws")
+
+
+def dense_workspace(n_units: int, device="cuda"):
+    """Device workspace of encode_dense_batch (capnp_packed_encode_dense_workspace_bytes); the
+    call zeroes it itself. Two calls in flight must not share one."""
+    nbytes = lib().capnp_packed_encode_dense_workspace_bytes(n_units)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def encode_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, base=0, cap=None, stream=None,
+                       ws=None, dialect="zig") -> None:
+    """Batch writePackedTo on one writer (capnp_packed_encode_dense_batch): the units packed
+    back to back into d_out[base ..) in unit order, in one pass. out_off (n + 1 entries) gets
+    the running offsets (out_off[0] = base, out_off[n] = the stream's end), out_len / status
+    are per unit. cap: the stream may use d_out[0 : cap) (None: all of d_out); a unit that
+    would end past it is not written and gets OUT_OF_SPACE, the offsets go on. d_out=None:
+    sizes and offsets only. ws: a dense_workspace() tensor (None: one is allocated for the call)."""
+    d = _dialect(dialect)
+    n = _units(in_off, in_len, out_len, status)
+    if out_off is not None and out_off.numel() < n + 1:
+        raise InvalidArgument(f"out_off has {out_off.numel()} entries for {n} units (n + 1 needed)")
+    if cap is None:
+        cap = 0 if d_out is None else d_out.numel()
+    if ws is None and n:
+        ws = dense_workspace(n, device=in_off.device)
+    _raise(lib().capnp_packed_encode_dense_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base, cap,
+                                                 _ptr(out_off), _ptr(out_len), _ptr(status), d, *_ws(ws),
+                                                 _stream(stream)), "encode_dense_batch")
 
 
 def encoded_size_batch(d_in, in_off, in_len, out_len, status, stream=None, dialect="zig") -> None:

@@ -468,6 +468,34 @@ int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_
     return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode launch");
 }
 
+size_t capnp_packed_encode_dense_workspace_bytes(uint32_t n) { return cpk::dense_workspace_bytes(n); }
+
+// Every argument check answers before any device work.
+int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                    uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
+                                    uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
+                                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (n == 0 && !d_out_off) return CAPNP_PACKED_OK;
+    if (n) {
+        if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
+        if (reinterpret_cast<uintptr_t>(d_workspace) & 255)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "workspace not 256-B aligned");
+        if (workspace_bytes < cpk::dense_workspace_bytes(n))
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT,
+                        "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
+    }
+    int st = ensure_device();
+    if (st) return st;
+    hipError_t e = cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
+                                            d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, d_workspace,
+                                            static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "dense encode launch");
+}
+
 int capnp_packed_encoded_size_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint64_t* d_out_len, int32_t* d_status, void* stream) {
     int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);

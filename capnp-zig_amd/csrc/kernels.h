@@ -81,6 +81,16 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
                                      const uint64_t* out_cap, uint64_t* out_len, int32_t* status, bool write,
                                      hipStream_t stream);
 
+// MessageBuilder.writePackedTo unit after unit on one writer (message.zig:2209-2213): the batch
+// packed into ONE dense stream out[out_base ..) in unit order, out_off[i] / out_off[n] the
+// running offsets, in one pass over the input (encode_dense_kernel: an ordered single-pass
+// prefix over tiles of units with decoupled look-back). out null: sizes and
+// offsets only. ws: dense_workspace_bytes(n) bytes, 256-B aligned, zeroed here on every call.
+size_t dense_workspace_bytes(uint32_t n);
+hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                               uint8_t* out, uint64_t out_base, uint64_t out_cap, uint64_t* out_off,
+                               uint64_t* out_len, int32_t* status, bool cxx, void* ws, hipStream_t stream);
+
 // Message.init segment-table parse (message.zig:341-394).
 hipError_t launch_message_init(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint32_t max_segs, uint32_t* seg_count, uint64_t* seg_off, uint64_t* seg_len,

@@ -50,6 +50,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "capnp_packed.h"
@@ -580,11 +581,17 @@ __device__ __forceinline__ void encode_lookahead(const uint8_t* src, uint32_t nw
 // indices; tb = 0 for a single tile). SINGLE: the whole unit (no carries; run
 // crossings are tested per lane boundary). Returns the tile's packed size; writes
 // the packed bytes to dst when WRITE and they fit in `room`.
-template <bool WRITE, bool SINGLE, bool FULL = false>
+//
+// HOOK (encode_dense_kernel): a caller that learns the destination only from the tile's size.
+// hook->place(P, dst) runs once P is known, with the tile's words still in registers; it sets
+// dst and answers whether to write. NoTileHook: dst / room are the caller's, as ever.
+struct NoTileHook {};
+template <bool WRITE, bool SINGLE, bool FULL = false, class HOOK = NoTileHook>
 __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lut, uint32_t lane, uint32_t words,
                                                 uint32_t tb, uint32_t& cz_c, uint32_t& cf_c, uint32_t nbz,
                                                 uint32_t nbf, uint8_t* dst, uint64_t room,
-                                                const uint8_t* direct = nullptr, const uint4* pre = nullptr) {
+                                                const uint8_t* direct = nullptr, const uint4* pre = nullptr,
+                                                HOOK* hook = nullptr) {
     const uint32_t wend = tb + words;  // absolute end of the tile
     // ---- lane j owns words [tb + 8j, tb + 8j + 8) --------------------------------
     const uint32_t base = tb + lane * 8;
@@ -704,7 +711,11 @@ __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lu
     const uint32_t o = incl - total;
     cz_c = lz_all;
     cf_c = lf_all;
-    if (!WRITE || (uint64_t)P > room) return P;
+    if constexpr (!std::is_same<HOOK, NoTileHook>::value) {
+        if (!hook->place(P, dst) || !WRITE) return P;
+    } else {
+        if (!WRITE || (uint64_t)P > room) return P;
+    }
 
     // ---- assemble the packed bytes in LDS (reusing the staging slice) -------------
     const uint32_t so = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15);
@@ -1120,11 +1131,11 @@ __device__ __forceinline__ void tile_words_direct(uint64_t (&w)[8], const uint8_
 // still open at the tile start. nbz / nbs: the first Z / stretch break at or after the tile
 // end. Per-word values (origins, run ends, sizes, counts) are derived from the lane's class
 // masks where they are used, not kept in arrays (95 VGPRs in the one-tile kernel, not 123).
-template <bool WRITE>
+template <bool WRITE, class HOOK = NoTileHook>
 __device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t* lut, uint32_t lane, uint32_t words,
                                                     uint32_t tb, bool single, uint32_t& cz_c, uint32_t& ch_c,
                                                     uint32_t nbz, uint32_t nbs, uint8_t* dst, uint64_t room,
-                                                    const uint64_t (&w)[8]) {
+                                                    const uint64_t (&w)[8], HOOK* hook = nullptr) {
     const uint32_t wend = tb + words;
     const uint32_t base = tb + lane * 8;
     const uint32_t nw = lane * 8 < words ? min(8u, words - lane * 8) : 0u;
@@ -1268,7 +1279,11 @@ __device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t
     const uint32_t ob = incl - total;
     cz_c = lz_all;
     ch_c = ch_out;
-    if (!WRITE || (uint64_t)P > room) return P;
+    if constexpr (!std::is_same<HOOK, NoTileHook>::value) {  // encode_tile's HOOK
+        if (!hook->place(P, dst) || !WRITE) return P;
+    } else {
+        if (!WRITE || (uint64_t)P > room) return P;
+    }
 
     // ---- assemble in LDS and write back, as encode_tile ----------------------------------
     const uint32_t so = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15);
@@ -1573,6 +1588,394 @@ __global__ __launch_bounds__(kBlock) void encode_message_cxx_kernel(const uint64
         status[msg] = (WRITE && !fits) ? ST_SPACE : ST_OK;
     }
 }
+
+// ---------------------------------------------------------------------------
+// ENCODE into one dense stream (capnp_packed_encode_dense_batch):
+// MessageBuilder.writePackedTo called unit after unit on one writer (message.zig:2209-2213).
+// Unit i's packed bytes start where unit i - 1's end, so a unit's destination is an ordered
+// prefix sum over the sizes of all units before it. One launch computes it with a
+// single-pass scan with decoupled look-back over TILES of kDnWaves units (a wave per unit):
+//   - a workgroup draws a ticket (one agent-scope add): its tile. Tiles are never tied to
+//     blockIdx, so a tile only ever waits for tiles whose workgroups already run. (Several
+//     tiles per ticket, one after another, serialise the whole launch: a ticket's first tile
+//     waits for the LAST tile of the ticket before it, which that workgroup sizes only after
+//     it has finished its earlier ones. Measured: DESIGN.md §2.10.)
+//   - every wave stages and sizes its unit (encode_tile up to P, the words still in
+//     registers; a unit of more than one tile: its size, from encode_dense_long_kernel);
+//   - the workgroup sums the sizes, wave 0 publishes the tile's AGGREGATE, looks back over
+//     the descriptors before it, 64 per load, until it meets an INCLUSIVE prefix, publishes
+//     its own inclusive prefix and hands each wave its offset;
+//   - assembly and write-back as in encode_kernel (store_partial16 is byte-granular: units of
+//     different workgroups share 16-B chunks and cache lines).
+// A descriptor is one aligned u64, state in bits 63:62 (0 empty, never published), value in
+// the low 62; written by one relaxed agent-scope atomic store and polled by relaxed
+// agent-scope atomic loads (vector path). Nothing else passes between workgroups.
+// Every spin is bounded by the constant-rate clock: on give-up the tile sets the give-up word,
+// publishes a POISONED descriptor (its successors give up too) and reports DEVICE_ERROR.
+// ---------------------------------------------------------------------------
+#ifndef CPK_DN_WAVES  // dev builds (scripts/dev/build_variant.sh): 8 or 16
+#define CPK_DN_WAVES 16
+#endif
+constexpr uint32_t kDnWaves = CPK_DN_WAVES;       // units per tile = waves per workgroup
+constexpr uint32_t kDnBlock = kDnWaves * kWave;
+// workspace, u64 words: 0 ticket counter (low u32), 1 give-up word, 2 longest look-back that
+// had to wait (ticks of the 100 MHz clock), 3 spare; descriptors from kDnHead on
+constexpr uint32_t kDnHead = 4;
+constexpr uint64_t kDnAgg = 1ull << 62, kDnIncl = 2ull << 62, kDnPoison = 3ull << 62;
+constexpr uint64_t kDnValue = (1ull << 62) - 1;
+#ifndef CPK_DN_HOP
+#define CPK_DN_HOP 1
+#endif
+constexpr uint32_t kDnHop = CPK_DN_HOP;           // windows of 64 descriptors a look-back hop loads
+#ifndef CPK_DN_SLEEP
+#define CPK_DN_SLEEP 8
+#endif
+constexpr int kDnSleep = CPK_DN_SLEEP;            // s_sleep between two polls (units of 64 clocks)
+constexpr uint64_t kDnSpinTicks = 200000000ull;   // 2 s: the bound of a look-back's whole wait
+typedef __attribute__((address_space(1))) uint64_t dn_gu64;
+
+// A u64 of lane `l` (-1: the first active lane) as a wave-uniform value. The halves go
+// through uint32_t: the builtins return int, and an int | u64 would sign-extend the low half
+// (offsets pass 2 GiB here).
+__device__ __forceinline__ uint64_t dn_uniform64(uint64_t v, int l = -1) {
+    const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    const uint32_t ulo = l < 0 ? (uint32_t)__builtin_amdgcn_readfirstlane(lo) : (uint32_t)__builtin_amdgcn_readlane(lo, l);
+    const uint32_t uhi = l < 0 ? (uint32_t)__builtin_amdgcn_readfirstlane(hi) : (uint32_t)__builtin_amdgcn_readlane(hi, l);
+    return (uint64_t)ulo | ((uint64_t)uhi << 32);
+}
+// inclusive sum of a u64 over the wave (wave_sum64's DPP steps)
+__device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t v) {
+#define CPK_SUM64_STEP(CTRL, ROWS)                                                              \
+    v += (uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)v, 0u) | ((uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)(v >> 32), 0u) << 32)
+    CPK_SUM64_STEP(0x111, 0xF);
+    CPK_SUM64_STEP(0x112, 0xF);
+    CPK_SUM64_STEP(0x114, 0xF);
+    CPK_SUM64_STEP(0x118, 0xF);
+    CPK_SUM64_STEP(0x142, 0xA);
+    CPK_SUM64_STEP(0x143, 0xC);
+#undef CPK_SUM64_STEP
+    return v;
+}
+
+__host__ __device__ inline uint64_t dense_tiles(uint64_t n) { return (n + kDnWaves - 1) / kDnWaves; }
+
+// Exclusive prefix of `tile` (> 0): the sum of every earlier tile's aggregate. All lanes of
+// one wave; false: gave up (the bound, or a poisoned predecessor).
+__device__ __forceinline__ bool dense_lookback(dn_gu64* ws, uint32_t tile, uint32_t lane, uint64_t& excl_out) {
+    dn_gu64* const desc = ws + kDnHead;
+    uint64_t excl = 0;
+    int64_t end = tile;  // this hop's window: tiles [end - 64, end), lane l reads tile end - 1 - l
+    const uint64_t t0 = wall_clock64();
+    bool waited = false;
+    for (;;) {  // wave-uniform; a hop loads kDnHop windows of 64 descriptors at once
+        uint64_t d[kDnHop];
+#pragma unroll
+        for (uint32_t k = 0; k < kDnHop; ++k) {
+            const int64_t idx = end - 1 - (int64_t)lane - 64 * (int64_t)k;
+            d[k] = kDnIncl;  // before tile 0: an inclusive prefix of 0
+            if (idx >= 0) d[k] = __hip_atomic_load(desc + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        bool done = false, stall = false;
+#pragma unroll
+        for (uint32_t k = 0; k < kDnHop; ++k) {  // nearest window first
+            if (done || stall) continue;
+            const uint32_t state = (uint32_t)(d[k] >> 62);
+            const uint64_t stop = __builtin_amdgcn_ballot_w64(state >= 2u);   // inclusive or poisoned
+            const uint64_t empty = __builtin_amdgcn_ballot_w64(state == 0u);
+            const uint64_t poison = __builtin_amdgcn_ballot_w64(state == 3u);
+            const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;  // the nearest prefix
+            const uint64_t need = first >= 63u ? ~0ull : (2ull << first) - 1ull;  // lanes 0 .. first
+            if (empty & need) {  // a tile between has not published yet: poll again from here
+                stall = true;
+                continue;
+            }
+            if (poison & need) {
+                if (lane == 0) __hip_atomic_store(ws + 1, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+            excl += dn_uniform64(wave_incl_sum64(lane <= first ? (d[k] & kDnValue) : 0ull), kWave - 1);
+            if (first < 64u) done = true;
+            else end -= 64;
+        }
+        if (done) break;
+        if (stall) {
+            if ((uint64_t)wall_clock64() - t0 > kDnSpinTicks) {
+                if (lane == 0) __hip_atomic_store(ws + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+            waited = true;
+            __builtin_amdgcn_s_sleep(kDnSleep);
+        }
+    }
+    if (waited && lane == 0) {  // the longest wait, for the record (rare: a load, then a max)
+        const uint64_t dt = wall_clock64() - t0;
+        if (dt > __hip_atomic_load(ws + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            __hip_atomic_fetch_max(ws + 2, dt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    excl_out = excl;
+    return true;
+}
+
+// One wave's view of its unit in a tile; place() is encode_tile's HOOK. Every wave of the
+// workgroup calls resolve() exactly once per tile (it holds the workgroup's two barriers).
+struct DenseUnit {
+    uint64_t* sx;      // LDS: kDnWaves sizes, kDnWaves offsets, the tile's verdict
+    dn_gu64* ws;
+    uint8_t* out;
+    uint64_t out_base, out_cap;
+    uint64_t* out_off;
+    uint64_t* out_len;
+    int32_t* status;
+    uint32_t tile, ntiles, n, unit, wave, lane;
+    int32_t st;        // the unit's input status
+    bool live, write;
+    uint64_t off;      // the unit's offset in out (resolve)
+
+    __device__ __forceinline__ bool resolve(uint64_t P) {
+        if (lane == 0) sx[wave] = P;
+        __syncthreads();
+        if (wave == 0) {
+            uint64_t pre = 0, tot = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < kDnWaves; ++j) {
+                const uint64_t v = sx[j];
+                tot += v;
+                pre += j < lane ? v : 0ull;
+            }
+            dn_gu64* const me = ws + kDnHead + tile;
+            uint64_t excl = 0;
+            bool good = true;
+            if (tile != 0) {
+                if (lane == 0) __hip_atomic_store(me, kDnAgg | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                good = dense_lookback(ws, tile, lane, excl);
+            }
+            if (lane == 0) {
+                __hip_atomic_store(me, good ? kDnIncl | (excl + tot) : kDnPoison, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+                sx[2 * kDnWaves] = good ? 1ull : 0ull;
+                if (tile + 1 == ntiles) out_off[n] = out_base + (good ? excl + tot : 0ull);
+            }
+            if (lane < kDnWaves) sx[kDnWaves + lane] = good ? excl + pre : 0ull;
+        }
+        __syncthreads();
+        // wave-uniform values out of LDS: back to scalar registers (the write-back's addresses)
+        const uint64_t rel = sx[kDnWaves + wave];
+        off = out_base + dn_uniform64(rel);
+        const bool good = __builtin_amdgcn_readfirstlane((uint32_t)sx[2 * kDnWaves]) != 0;
+        if (!live) return false;
+        int32_t s2 = st;
+        uint64_t len = st == ST_OK ? P : 0ull;
+        bool wr = false;
+        if (!good) {
+            s2 = ST_DEVERR;
+            len = 0;
+        } else if (st == ST_OK && write && P != 0) {
+            // the unit's end must not pass out_cap (no wrap: compare against the room)
+            if (off > out_cap || P > out_cap - off) s2 = ST_SPACE;
+            else wr = true;
+        }
+        if (lane == 0) {
+            out_off[unit] = off;
+            out_len[unit] = len;
+            status[unit] = s2;
+        }
+        return wr;
+    }
+    __device__ __forceinline__ bool place(uint32_t P, uint8_t*& dst) {
+        const bool wr = resolve(P);
+        dst = out + off;
+        return wr;
+    }
+};
+
+// A unit of more than one tile under the Zig rule, tile by tile as encode_tiled_kernel walks
+// it: the packed size (WRITE: and the bytes, to dst, which holds them all).
+template <bool WRITE>
+__device__ __forceinline__ uint64_t dense_long_zig(uint8_t* lds, const uint64_t* lut, uint32_t lane,
+                                                   const uint8_t* src, uint32_t words, uint8_t* dst) {
+    uint32_t cz = 0, cf = 0;
+    uint64_t pos = 0;
+    for (uint32_t tb = 0; tb < words; tb += kEncMaxWords) {
+        uint32_t lane_u = lane;
+        asm volatile("" : "+v"(lane_u));
+        const uint32_t tw = min(kEncMaxWords, words - tb);
+        const uint32_t te = tb + tw;
+        uint4 v[5];
+        encode_load(v, src + 8ull * tb, tw, lane_u);
+        uint32_t nbz = words, nbf = words;
+        if (te < words) {
+            const uint32_t la = min(256u, words - te);
+            uint32_t bz, bf;
+            encode_lookahead(src + 8ull * te, la, lane_u, bz, bf);
+            nbz = bz < la ? te + bz : (la == 256u ? te + 256u : words);
+            nbf = bf < la ? te + bf : (la == 256u ? te + 256u : words);
+        }
+        wave_lds_sync();  // the previous tile's write-back read the slice
+        encode_put(lds, v, (uint32_t)(reinterpret_cast<uintptr_t>(src + 8ull * tb) & 15), tw, lane_u);
+        wave_lds_sync();
+        pos += encode_tile<WRITE, false>(lds, lut, lane_u, tw, tb, cz, cf, nbz, nbf, dst + pos, WRITE ? ~0ull : 0ull);
+    }
+    return pos;
+}
+
+// One tile of the dense stream: the wave's unit is tile * kDnWaves + wave.
+template <bool WRITE, bool CXX>
+__device__ __forceinline__ void dense_tile(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                           const uint64_t* __restrict__ in_len, uint8_t* lds, const uint64_t* lut,
+                                           DenseUnit& du) {
+    const uint32_t lane = du.lane;
+    const uint32_t unit = du.unit;
+    const bool live = du.live;
+    const uint64_t b0 = live ? in_off[unit] : 0ull, nbytes = live ? in_len[unit] : 0ull;
+    const uint8_t* const src = in + b0;
+    int32_t st = ST_OK;
+    if (reinterpret_cast<uintptr_t>(src) & 7) st = ST_ARG;
+    else if (nbytes & 7) st = ST_SIZE;  // message.zig:201
+    else if ((nbytes >> 3) > 0xFFFFF000ull) st = ST_ARG;  // word indices are u32; no serial path here
+    du.st = st;
+    if (!live || st != ST_OK) {
+        du.resolve(0);
+        return;
+    }
+    const uint32_t words = (uint32_t)(nbytes >> 3);
+    if (words <= kEncMaxWords) {
+        // a full 16-B aligned tile (the headline's units): the lane's 64 B straight from memory
+        const bool direct = words == kEncMaxWords && !(reinterpret_cast<uintptr_t>(src) & 15);
+        if (CXX) {
+            uint64_t w[8];
+            if (direct) {
+                tile_words_direct(w, src, lane);
+            } else {
+                encode_stage(lds, src, words, lane);
+                wave_lds_sync();
+                tile_words_lds(w, lds, lane, words);
+            }
+            uint32_t cz = 0, ch = 0;
+            encode_tile_cxx<WRITE, DenseUnit>(lds, lut, lane, words, 0, true, cz, ch, words, words, nullptr, 0, w, &du);
+        } else {
+            uint32_t cz = 0, cf = 0;
+            if (direct) {
+                encode_tile<WRITE, true, true, DenseUnit>(lds, lut, lane, words, 0, cz, cf, words, words, nullptr, 0,
+                                                          src, nullptr, &du);
+            } else {
+                encode_stage(lds, src, words, lane);
+                wave_lds_sync();
+                encode_tile<WRITE, true, false, DenseUnit>(lds, lut, lane, words, 0, cz, cf, words, words, nullptr, 0,
+                                                           nullptr, nullptr, &du);
+            }
+        }
+        return;
+    }
+    // More than one tile: the unit needs its total size before its first byte is written, so
+    // its tile loop runs twice, both times in encode_dense_long_kernel (the loops in here had
+    // this kernel at 140-163 VGPRs, one workgroup per CU): the size pass ran before this
+    // kernel and left the size in out_len, the write pass follows it.
+    du.resolve(du.out_len[unit]);
+}
+
+// The two tile loops of the units of more than one tile, a launch each side of
+// encode_dense_kernel: WRITE false, the sizes into out_len; WRITE true, the bytes to the offsets
+// encode_dense_kernel gave them (status OK: the unit fits below out_cap). A small grid strides
+// over the batch's lengths, 64 per load, as encode_cxx_long_kernel does; a long unit is one
+// wave's work and its input is read twice.
+template <bool WRITE, bool CXX>
+__global__ __launch_bounds__(kBlock) void encode_dense_long_kernel(const uint8_t* __restrict__ in,
+                                                                   const uint64_t* __restrict__ in_off,
+                                                                   const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                   uint8_t* out, const uint64_t* out_off,
+                                                                   uint64_t* out_len, const int32_t* status,
+                                                                   uint64_t* ws, uint64_t ws_words) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    } else {
+        // the launch ahead of encode_dense_kernel also zeroes its workspace (ticket, give-up
+        // word, every descriptor), on every call
+        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ws_words; i += (uint64_t)gridDim.x * kBlock)
+            ws[i] = 0;
+    }
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kWave;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kWave; ubase < n; ubase += stride) {
+        const uint64_t u = ubase + lane;
+        bool mine = false;
+        if (u < n) {
+            const uint64_t len = in_len[u];
+            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && (len >> 3) > kEncMaxWords &&
+                   (len >> 3) <= 0xFFFFF000ull;
+            if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
+        }
+        uint64_t todo = __ballot(mine);
+        while (todo) {  // wave-uniform
+            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint8_t* const src = in + in_off[unit];
+            const uint32_t words = (uint32_t)(in_len[unit] >> 3);
+            uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
+            uint64_t pos = 0;
+            if (CXX) {
+                bool fits = true;
+                encode_piece_cxx<WRITE>(lds, lut, lane, src, words, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
+            } else {
+                pos = dense_long_zig<WRITE>(lds, lut, lane, src, words, dst);
+            }
+            if (!WRITE && lane == 0) out_len[unit] = pos;
+        }
+    }
+}
+
+// Register target: 16 waves are one workgroup per CU (82 KB of LDS), 4 waves per SIMD. (With 8
+// waves the LDS admits three workgroups per CU, 80 VGPRs: the Zig tile fits that, the C++ tile,
+// 95 VGPRs as it comes, does not and runs at two.)
+template <bool WRITE, bool CXX>
+__global__ __launch_bounds__(kDnBlock, (CXX || kDnWaves > 8) ? 4 : 6) void encode_dense_kernel(const uint8_t* __restrict__ in,
+                                                                const uint64_t* __restrict__ in_off,
+                                                                const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                uint8_t* out, uint64_t out_base, uint64_t out_cap,
+                                                                uint64_t* out_off, uint64_t* out_len,
+                                                                int32_t* status, uint64_t* ws_) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kDnWaves * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    __shared__ __attribute__((aligned(16))) uint64_t sx[2 * kDnWaves + 2];
+    dn_gu64* const ws = reinterpret_cast<dn_gu64*>(reinterpret_cast<uintptr_t>(ws_));
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x == 0)
+        sx[2 * kDnWaves + 1] = __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>(ws),
+                                                      1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (WRITE && threadIdx.x < 256) lut[threadIdx.x] = compact_selector(threadIdx.x);
+    __syncthreads();
+    const uint32_t ticket = __builtin_amdgcn_readfirstlane((uint32_t)sx[2 * kDnWaves + 1]);
+    const uint32_t ntiles = (uint32_t)dense_tiles(n);
+    DenseUnit du;
+    du.sx = sx;
+    du.ws = ws;
+    du.out = out;
+    du.out_base = out_base;
+    du.out_cap = out_cap;
+    du.out_off = out_off;
+    du.out_len = out_len;
+    du.status = status;
+    du.ntiles = ntiles;
+    du.n = n;
+    du.wave = wave;
+    du.lane = lane;
+    du.write = WRITE;
+    du.off = 0;
+    uint8_t* const lds = smem + wave * kEncLds;
+    if (ticket >= ntiles) return;  // block-uniform (the grid is ntiles workgroups: never)
+    du.tile = ticket;
+    const uint64_t unit = (uint64_t)ticket * kDnWaves + wave;
+    du.live = unit < n;
+    du.unit = du.live ? (uint32_t)unit : 0u;
+    dense_tile<WRITE, CXX>(in, in_off, in_len, lds, lut, du);
+}
+
+__global__ void store_u64_kernel(uint64_t* p, uint64_t v) { *p = v; }
 
 // ---------------------------------------------------------------------------
 // ENCODE straight from segment lists: MessageBuilder.toPackedBytes
@@ -6612,6 +7015,53 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
     else
         encode_message_cxx_kernel<false><<<blocks, kBlock, 0, stream>>>(seg_ptr, seg_len, seg_first, seg_count, n, out,
                                                                         out_off, out_cap, out_len, status);
+    return hipGetLastError();
+}
+
+// The dense stream (encode_dense_kernel): the ticket, the give-up word and every descriptor are
+// zeroed on every call, ahead of the launch, by the long units' size pass (the whole workspace,
+// a multiple of 256 bytes). Not by hipMemsetAsync: captured by torch.cuda.graph, its node
+// filled the workspace with a stray 16-byte pattern on replay (ROCm 7.2).
+size_t dense_workspace_bytes(uint32_t n) {
+    const size_t bytes = 8 * ((size_t)kDnHead + (size_t)dense_tiles(n));
+    return (bytes + 255) & ~(size_t)255;
+}
+
+hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                               uint8_t* out, uint64_t out_base, uint64_t out_cap, uint64_t* out_off,
+                               uint64_t* out_len, int32_t* status, bool cxx, void* ws, hipStream_t stream) {
+    if (n == 0) {
+        if (!out_off) return hipSuccess;
+        store_u64_kernel<<<1, 1, 0, stream>>>(out_off, out_base);
+        return hipGetLastError();
+    }
+    const uint32_t blocks = (uint32_t)dense_tiles(n);
+    uint64_t* const w = static_cast<uint64_t*>(ws);
+#define CPK_DENSE(W, C)                                                                                          \
+    encode_dense_kernel<W, C><<<blocks, kDnBlock, 0, stream>>>(in, in_off, in_len, n, out, out_base, out_cap, \
+                                                               out_off, out_len, status, w)
+    // the units of more than one tile: their sizes before, their bytes after (no such unit: one
+    // pass over the lengths each)
+    const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
+#define CPK_DENSE_LONG(W, C)                                                                                     \
+    encode_dense_long_kernel<W, C><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_len, \
+                                                                       status, w, dense_workspace_bytes(n) / 8)
+    if (cxx) CPK_DENSE_LONG(false, true);
+    else CPK_DENSE_LONG(false, false);
+    if (out) {
+        if (cxx) {
+            CPK_DENSE(true, true);
+            CPK_DENSE_LONG(true, true);
+        } else {
+            CPK_DENSE(true, false);
+            CPK_DENSE_LONG(true, false);
+        }
+    } else {
+        if (cxx) CPK_DENSE(false, true);
+        else CPK_DENSE(false, false);
+    }
+#undef CPK_DENSE_LONG
+#undef CPK_DENSE
     return hipGetLastError();
 }
 

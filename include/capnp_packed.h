@@ -46,7 +46,9 @@ extern "C" {
  *     (capnp_packed_set_decoder is the only selector). Round 6 changed no signature.
  *   2, additions only: CAPNP_PACKED_DIALECT_ZIG / _CXX and capnp_packed_encode_dialect,
  *     capnp_packed_encode_batch_dialect, capnp_packed_encode_message_batch_dialect (the opt-in
- *     C++-canonical encoder). Nothing that existed changed. */
+ *     C++-canonical encoder). Nothing that existed changed.
+ *   2, additions only: capnp_packed_encode_dense_workspace_bytes and
+ *     capnp_packed_encode_dense_batch (the batch form of writePackedTo). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -365,6 +367,50 @@ int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const u
                                               uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                               uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
                                               void* stream);
+
+/* ---------------------------------------------------------------------------
+ * One dense packed stream: MessageBuilder.writePackedTo(writer) called for unit 0, 1, ...
+ * n-1 on one writer (message.zig:2209-2213), in ONE pass over the input: no size pass, no
+ * caller-side scan, no capacity slots.
+ *   d_out_off[0] = out_base, d_out_off[i + 1] = d_out_off[i] + d_out_len[i]  (n + 1 entries);
+ *   unit i's packed bytes are d_out[d_out_off[i] .. + d_out_len[i]), in unit order: the
+ *   stream is the concatenation of packPacked(unit_i) (DIALECT_CXX: each unit one piece), byte
+ *   for byte what encoded_size_batch -> lengths_to_offsets -> encode_batch writes.
+ * out_base may be any byte value (odd ones append to a stream that already holds bytes);
+ * d_out_off / d_out_len can be passed on unchanged as a decode's or
+ * capnp_packed_read_message_batch's (in_off, in_len).
+ * Per-unit input errors: a word side that is not 8-aligned INVALID_ARGUMENT, len % 8 != 0
+ * INVALID_MESSAGE_SIZE, and a unit of more than 0xFFFFF000 words INVALID_ARGUMENT (this call
+ * has no serial path for such units). Such a unit gets d_out_len 0, takes no bytes, and the
+ * stream goes on.
+ * Space: the stream may use d_out[0 .. out_cap). A unit with d_out_len > 0 whose end
+ * d_out_off[i + 1] exceeds out_cap is not written and gets OUT_OF_SPACE; its d_out_len is
+ * still its packed size and the offsets keep accumulating, so d_out_off[n] is the end a retry
+ * needs. Units that end at or below out_cap are written and OK; a unit with nothing to write
+ * is OK wherever it lands. No byte at or past d_out + out_cap and none below d_out + out_base
+ * is ever written.
+ * d_out == NULL: sizes and offsets only (out_cap is ignored): one call instead of
+ * encoded_size_batch + lengths_to_offsets.
+ * dialect: CAPNP_PACKED_DIALECT_ZIG or _CXX; anything else INVALID_ARGUMENT before any device
+ * work.
+ * d_workspace: caller-owned device memory, 256-B aligned, at least
+ * capnp_packed_encode_dense_workspace_bytes(n) bytes, required for n > 0 (NULL, misaligned or
+ * short: INVALID_ARGUMENT). The call zeroes it on `stream` every time; the library keeps no
+ * state for this call and allocates nothing, so it is asynchronous and capturable in a
+ * hipGraph. Two calls in flight must not share a workspace.
+ * n == 0 is OK: d_out_off[0] = out_base when d_out_off is non-NULL, no device work when it is
+ * NULL. The return value reports argument and launch errors only. A unit status of
+ * DEVICE_ERROR means the kernel's bounded wait for an earlier unit's offset ran out (2 s of the
+ * device's constant-rate clock; never expected. A single unit whose own encode takes longer
+ * than that, on the order of a GiB, makes the units after it give up).
+ * Units of at most 64 words take a wave each here, as in the C++ dialect.
+ * ------------------------------------------------------------------------ */
+size_t capnp_packed_encode_dense_workspace_bytes(uint32_t n);
+int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                    uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
+                                    uint64_t* d_out_off /* n + 1 */, uint64_t* d_out_len /* n */,
+                                    int32_t* d_status /* n */, uint32_t dialect, void* d_workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* Message.init (message.zig:341-394) segment-table parse of n framed messages
  * d_in[d_in_off[i] .. + d_in_len[i]) (e.g. the output of a decode batch).

@@ -154,6 +154,17 @@ pub extern "capnp_packed" fn capnp_packed_encode_batch_dialect(
     d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64,
     d_out_len: [*]u64, d_status: [*]i32, dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
 ) c_int;
+/// The batch form of `MessageBuilder.writePackedTo` on one writer: n units packed back to back
+/// into `d_out[out_base ..)` in one pass; `d_out_off` has n + 1 entries (running offsets), a
+/// null `d_out` gives sizes and offsets only. `d_ws`: `capnp_packed_encode_dense_workspace_bytes(n)`
+/// bytes of device memory, 256-B aligned, not shared between calls in flight.
+pub extern "capnp_packed" fn capnp_packed_encode_dense_workspace_bytes(n: u32) usize;
+pub extern "capnp_packed" fn capnp_packed_encode_dense_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    d_out: ?[*]u8, out_base: u64, out_cap: u64,
+    d_out_off: [*]u64, d_out_len: [*]u64, d_status: [*]i32,
+    dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
+) c_int;
 pub extern "capnp_packed" fn capnp_packed_decode_batch_ws(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
     d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u64,
