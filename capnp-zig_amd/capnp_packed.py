@@ -230,6 +230,8 @@ SIGNATURES = {
     "capnp_packed_framer_expected": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
     "capnp_packed_framer_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64),
                                                  ctypes.POINTER(ctypes.c_uint64)]),
+    "capnp_packed_framer_walk_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64),
+                                                      ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 # capnp_packed_set_decoder values (include/capnp_packed.h)
@@ -705,6 +707,13 @@ class FramerSession:
         up, mv = ctypes.c_uint64(), ctypes.c_uint64()
         _raise(lib().capnp_packed_framer_stats(self.handle, ctypes.byref(up), ctypes.byref(mv)), "framer_stats")
         return {"uploaded_bytes": up.value, "moved_bytes": mv.value}
+
+    def walk_stats(self) -> dict:
+        """Walk passes run and the windows they built lookup tables for."""
+        ps, tw = ctypes.c_uint64(), ctypes.c_uint64()
+        _raise(lib().capnp_packed_framer_walk_stats(self.handle, ctypes.byref(ps), ctypes.byref(tw)),
+               "framer_walk_stats")
+        return {"passes": ps.value, "table_windows": tw.value}
 
 
 class PackedFramer:

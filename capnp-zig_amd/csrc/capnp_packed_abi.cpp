@@ -842,6 +842,7 @@ struct capnp_packed_framer {
         }
     } pin_state, pin_tab, pin_units, pin_jobs;
     uint64_t uploaded = 0, moved = 0;  // bytes copied H2D (new reads) and moved between regions
+    uint64_t walk_passes = 0, table_windows = 0;  // walk passes run, windows they built tables for
     int dev = -1;                      // the device the session was created on
     static constexpr uint32_t kWalkMessages = 64;  // messages a walk pass finds per connection
 
@@ -1042,6 +1043,14 @@ int capnp_packed_framer_stats(capnp_packed_framer* f, uint64_t* uploaded, uint64
     std::lock_guard<std::mutex> lock(f->mu);
     *uploaded = f->uploaded;
     *moved = f->moved;
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_walk_stats(capnp_packed_framer* f, uint64_t* passes, uint64_t* table_windows) {
+    if (!f || !passes || !table_windows) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null pointer");
+    std::lock_guard<std::mutex> lock(f->mu);
+    *passes = f->walk_passes;
+    *table_windows = f->table_windows;
     return CAPNP_PACKED_OK;
 }
 
@@ -1287,6 +1296,8 @@ int framer_read_locked(capnp_packed_framer* f, const uint8_t* in, uint64_t in_by
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "framer walk pass");
         f->jobs_inflight = false;
+        ++f->walk_passes;
+        f->table_windows += T;
         // whole messages, in order per connection, while the frames buffer and table hold them:
         // decoded from the arena into frame slots, then to the caller's buffer
         um.clear();  // per message: in_off, in_len, out_off, out_cap

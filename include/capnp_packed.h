@@ -304,6 +304,11 @@ int capnp_packed_framer_expected(capnp_packed_framer* f, uint32_t conn, uint64_t
 /* Bytes copied host-to-device (every read's bytes once) and moved between device regions since
  * the session was made (a connection's bytes move when its region doubles). */
 int capnp_packed_framer_stats(capnp_packed_framer* f, uint64_t* uploaded, uint64_t* moved);
+/* Walk passes run since the session was made (a call of capnp_packed_framer_read / _readv, with
+ * or without new bytes, runs one per 64 messages of the connection with the most to walk, and none
+ * when no connection holds bytes) and the windows those passes built lookup tables for: 0 while
+ * every walk went window by window. Host-side counters, for tests and tuning. */
+int capnp_packed_framer_walk_stats(capnp_packed_framer* f, uint64_t* passes, uint64_t* table_windows);
 
 /* Single-buffer Reader.readPackedMessage on HOST memory: decodes the message at
  * the front of in[0..n) into out[0..*out_len); *consumed = packed bytes used.

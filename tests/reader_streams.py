@@ -140,8 +140,9 @@ def oracle_read(stream):
 
 # family: exact / zero_over / lit_over / lit_cut / trunc / header / random. kind and rend as the
 # generator built them (None where it did not build the last record): checked against read_message
-# on the sampled streams.
-Stream = collections.namedtuple("Stream", "data family kind rend")
+# on the sampled streams. mode: how the base message was written (hand / zig / cxx; None: not a
+# base's stream).
+Stream = collections.namedtuple("Stream", "data family kind rend mode", defaults=(None,))
 
 DENSITIES = ("literal", "mixed", "zero", "chain")
 SEGMENT_COUNTS = (1, 2, 3, 8, 64, 511, 512)
@@ -321,6 +322,72 @@ def _header_error_streams(rng, tails):
     return [Stream(s, "header", None, None) for s in out]
 
 
+def base_endings(rng, bi, fw, nseg, prefix, trailing, nexts, mode=None):
+    """The streams around one base message's framed-length cut (prefix: _build_base's): exact
+    with trailing bytes, a zero run or a literal run that passes the framed length, that literal
+    run cut, and the stream truncated before the framed length."""
+    streams = []
+    S = functools.partial(Stream, mode=mode)
+    bw = fw - (nseg // 2 + 1)
+    exact = prefix(0)
+    long_tail = 10 * fw + 40 - len(exact)
+    for j, t in enumerate((0, 1, 7, 24, long_tail)):
+        streams.append(S(exact + trailing(bi + j, t), "exact", None, None))
+    nxt = nexts[bi % len(nexts)]
+    streams.append(S(exact + nxt + _rand(rng, bi % 5), "exact", None, None))
+
+    # the last record replaces the last k words (all of them in the body; a table-only
+    # message ends in a zero word, which a zero run or a literal word can stand for)
+    kmax = max(1, min(bw, 255))
+    for j, over in enumerate((1, 16, 255) if bi % 2 else (2, 15, 100)):
+        k = min(kmax, 256 - over, (1, 3, 40)[j])
+        p = prefix(k)
+        rec = bytes((0, k + over - 1))
+        for jj, t in enumerate((0, 1, 7, 24, 10 * fw + 40 - len(p) - 2)):
+            if j and jj in (1, 2):
+                continue
+            streams.append(S(p + rec + trailing(bi + jj, t), "zero_over", "zero", len(p) + 2))
+
+    k = min(kmax, int(rng.integers(1, 9)))
+    p = prefix(k)
+    c = k + int(rng.integers(0, 30))
+    reach = -(-(10 * fw + 14 - len(p) - 10) // 8)  # the run's end passes 10 * fw + 12
+    if bi % 2 == 0 and reach <= 255:
+        c = max(c, reach)
+    c = min(c, 255)
+    first = bytes(8) if bw == 0 else _rand(rng, 8)
+    rec = b"\xff" + first + bytes((c,)) + _rand(rng, 8 * c)
+    rend = len(p) + len(rec)
+    ends = {rend - 9, rend - 8, rend - 1, rend, rend + 1, rend + 1500}
+    ends |= {10 * fw + d for d in range(-12, 13) if 10 * fw + d > len(p)}
+    full = p + rec
+    for j, e in enumerate(sorted(ends)):
+        if e < len(p) + 10:  # inside the record's first 9 bytes: no count byte, no run yet
+            streams.append(S(full[:e], "trunc", None, None))
+        elif e < rend:
+            streams.append(S(full[:e], "lit_cut", "lit", rend))
+        else:
+            streams.append(S(full + trailing(bi + j, e - rend), "lit_over", "lit", rend))
+
+    # the stream ends before the framed length: inside a tag's bytes, after a 00, inside an
+    # FF record's first 9 bytes (first and last such record), and one byte short
+    recs = _record_starts(exact)
+    cuts = {len(exact) - 1, len(exact) // 2, 1} | ({0} if bi % 16 == 0 else set())
+    for sel in (recs, recs[::-1]):
+        tagged = next((q for q, t in sel if t not in (0, 0xFF) and len(_TAG_POS[t]) >= 2), None)
+        zero = next((q for q, t in sel if t == 0), None)
+        lit = next((q for q, t in sel if t == 0xFF), None)
+        if tagged is not None:
+            cuts.add(tagged + 2)
+        if zero is not None:
+            cuts.add(zero + 1)
+        if lit is not None:
+            cuts |= {lit + 1, lit + 5, lit + 9}
+    for e in sorted(x for x in cuts if 0 <= x < len(exact)):
+        streams.append(S(exact[:e], "trunc", None, None))
+    return streams
+
+
 def corpus(seed):
     """The list of Stream for this seed (about 6,000 streams, under 24 MB)."""
     rng = np.random.default_rng(seed)
@@ -337,63 +404,7 @@ def corpus(seed):
 
     for bi, (fw, nseg, density, mode) in enumerate(_base_specs(rng)):
         prefix = _build_base(rng, fw, nseg, density, mode)
-        bw = fw - (nseg // 2 + 1)
-        exact = prefix(0)
-        long_tail = 10 * fw + 40 - len(exact)
-        for j, t in enumerate((0, 1, 7, 24, long_tail)):
-            streams.append(Stream(exact + trailing(bi + j, t), "exact", None, None))
-        nxt = nexts[bi % len(nexts)]
-        streams.append(Stream(exact + nxt + _rand(rng, bi % 5), "exact", None, None))
-
-        # the last record replaces the last k words (all of them in the body; a table-only
-        # message ends in a zero word, which a zero run or a literal word can stand for)
-        kmax = max(1, min(bw, 255))
-        for j, over in enumerate((1, 16, 255) if bi % 2 else (2, 15, 100)):
-            k = min(kmax, 256 - over, (1, 3, 40)[j])
-            p = prefix(k)
-            rec = bytes((0, k + over - 1))
-            for jj, t in enumerate((0, 1, 7, 24, 10 * fw + 40 - len(p) - 2)):
-                if j and jj in (1, 2):
-                    continue
-                streams.append(Stream(p + rec + trailing(bi + jj, t), "zero_over", "zero", len(p) + 2))
-
-        k = min(kmax, int(rng.integers(1, 9)))
-        p = prefix(k)
-        c = k + int(rng.integers(0, 30))
-        reach = -(-(10 * fw + 14 - len(p) - 10) // 8)  # the run's end passes 10 * fw + 12
-        if bi % 2 == 0 and reach <= 255:
-            c = max(c, reach)
-        c = min(c, 255)
-        first = bytes(8) if bw == 0 else _rand(rng, 8)
-        rec = b"\xff" + first + bytes((c,)) + _rand(rng, 8 * c)
-        rend = len(p) + len(rec)
-        ends = {rend - 9, rend - 8, rend - 1, rend, rend + 1, rend + 1500}
-        ends |= {10 * fw + d for d in range(-12, 13) if 10 * fw + d > len(p)}
-        full = p + rec
-        for j, e in enumerate(sorted(ends)):
-            if e < len(p) + 10:  # inside the record's first 9 bytes: no count byte, no run yet
-                streams.append(Stream(full[:e], "trunc", None, None))
-            elif e < rend:
-                streams.append(Stream(full[:e], "lit_cut", "lit", rend))
-            else:
-                streams.append(Stream(full + trailing(bi + j, e - rend), "lit_over", "lit", rend))
-
-        # the stream ends before the framed length: inside a tag's bytes, after a 00, inside an
-        # FF record's first 9 bytes (first and last such record), and one byte short
-        recs = _record_starts(exact)
-        cuts = {len(exact) - 1, len(exact) // 2, 1} | ({0} if bi % 16 == 0 else set())
-        for sel in (recs, recs[::-1]):
-            tagged = next((q for q, t in sel if t not in (0, 0xFF) and len(_TAG_POS[t]) >= 2), None)
-            zero = next((q for q, t in sel if t == 0), None)
-            lit = next((q for q, t in sel if t == 0xFF), None)
-            if tagged is not None:
-                cuts.add(tagged + 2)
-            if zero is not None:
-                cuts.add(zero + 1)
-            if lit is not None:
-                cuts |= {lit + 1, lit + 5, lit + 9}
-        for e in sorted(x for x in cuts if 0 <= x < len(exact)):
-            streams.append(Stream(exact[:e], "trunc", None, None))
+        streams += base_endings(rng, bi, fw, nseg, prefix, trailing, nexts, mode)
 
     streams += _header_error_streams(rng, nexts)
 
@@ -411,7 +422,7 @@ SEED = 0x5EED0007
 
 # One corpus stream with everything the tests derive from the references: the oracle's result
 # and read_message's header facts (fw, spans).
-Case = collections.namedtuple("Case", "data family kind rend status framed consumed fw spans")
+Case = collections.namedtuple("Case", "data family kind rend status framed consumed fw spans mode", defaults=(None,))
 
 
 @functools.lru_cache(maxsize=2)
@@ -420,7 +431,7 @@ def cases(seed=SEED):
     for s in corpus(seed):
         status, framed, used = oracle_read(s.data)
         h = read_message(s.data, header_only=True)
-        out.append(Case(s.data, s.family, s.kind, s.rend, status, framed, used, h.fw, h.spans))
+        out.append(Case(s.data, s.family, s.kind, s.rend, status, framed, used, h.fw, h.spans, s.mode))
     return out
 
 

@@ -23,7 +23,8 @@ def declared_functions():
 def test_header_declares_expected_surface():
     names = declared_functions()
     for must in ("capnp_packed_encode", "capnp_packed_decode", "capnp_packed_decoded_size",
-                 "capnp_packed_encode_batch", "capnp_packed_decode_batch", "capnp_packed_encode_bound"):
+                 "capnp_packed_encode_batch", "capnp_packed_decode_batch", "capnp_packed_encode_bound",
+                 "capnp_packed_framer_stats", "capnp_packed_framer_walk_stats"):
         assert must in names
 
 
@@ -126,7 +127,7 @@ def test_zig_binding_declares_only_header_symbols():
     zig = open(os.path.join(REPO, "zig", "packed_ffi.zig")).read()
     externs = set(re.findall(r'extern "capnp_packed" fn (capnp_packed_\w+)', zig))
     assert externs <= set(declared_functions()), externs - set(declared_functions())
-    assert "capnp_packed_validate_batch" in externs
+    assert "capnp_packed_validate_batch" in externs and "capnp_packed_framer_walk_stats" in externs
 
 
 def test_validate_argument_errors_without_device():

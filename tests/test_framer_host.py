@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import capnp_packed as cp
+import framer_streams
 import oracle
 import pyref
 
@@ -16,38 +17,7 @@ ORACLE_TO_ABI = {0: cp.OK, -1: cp.END_OF_STREAM, -2: cp.INVALID_SEGMENT_COUNT,
                  -3: cp.SEGMENT_COUNT_LIMIT_EXCEEDED, -6: cp.MESSAGE_TOO_LARGE, -7: cp.INVALID_PACKED_MESSAGE}
 
 
-class FakeSession:
-    """capnp_packed_framer_* restated on the oracle reader (test stand-in)."""
-
-    def __init__(self, n_conns):
-        self.n = n_conns
-        self.buf = [b""] * n_conns
-        self.calls = 0
-
-    def read(self, reads):
-        self.calls += 1
-        for c, d in reads.items():
-            self.buf[c] += bytes(d)
-        frames, status = {}, np.full(self.n, cp.END_OF_STREAM, dtype=np.int32)
-        for c in range(self.n):
-            while self.buf[c]:
-                rc, framed, used = oracle.read_packed_message(self.buf[c], cap=1 << 22)
-                rc = ORACLE_TO_ABI[rc]
-                if rc == cp.END_OF_STREAM:
-                    break
-                if rc != cp.OK:
-                    status[c] = rc
-                    self.buf[c] = b""  # the session drops a failed connection's bytes
-                    break
-                frames.setdefault(c, []).append(memoryview(framed))
-                self.buf[c] = self.buf[c][used:]
-        return frames, status
-
-    def buffered(self, c):
-        return len(self.buf[c])
-
-    def reset(self, c):
-        self.buf[c] = b""
+FakeSession = framer_streams.ModelSession  # capnp_packed_framer_* restated on the oracle reader
 
 
 def make_stream(rng, n_msgs):

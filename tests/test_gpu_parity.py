@@ -382,6 +382,23 @@ def test_lengths_to_offsets(n):
     assert (off == expect).all()
 
 
+@pytest.mark.parametrize("n", [2_097_152, 2_097_153, 2_099_201])
+def test_lengths_to_offsets_second_partials_step(n):
+    """scan_partials_kernel takes the tiles' partial sums 1024 at a time: 1024, 1025 and 1026
+    tiles of 2048 lengths (the second step's carry), a non-zero base, lengths of up to 2^31
+    among the small ones so that the running sum passes 2^32 early and often."""
+    rng = np.random.default_rng(n)
+    lens = rng.integers(0, 5000, size=n).astype(np.int64)
+    big = rng.integers(0, n, 64)
+    lens[big] = rng.integers(1 << 30, 1 << 31, 64)
+    lens[[0, 2047, 2048, 2048 * 1024 - 1, n - 1]] = (1 << 32) + 3
+    d = torch.from_numpy(lens).to(DEV)
+    base = (1 << 33) + 5
+    off = cp.lengths_to_offsets(d, base=base).cpu().numpy()
+    expect = np.concatenate([[base], base + np.cumsum(lens)])
+    assert off.shape == expect.shape and (off == expect).all()
+
+
 # ---------------------------------------------------------------------------
 # BASELINE configs
 # ---------------------------------------------------------------------------
