@@ -171,7 +171,7 @@ __device__ __forceinline__ uint32_t dpp_mov(uint32_t v, uint32_t ident) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)v, CTRL, ROWS, 0xF, false);
 }
 
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, uint32_t /*lane*/) {
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
     v += dpp_mov<0x111, 0xF>(v, 0u);
     v += dpp_mov<0x112, 0xF>(v, 0u);
     v += dpp_mov<0x114, 0xF>(v, 0u);
@@ -181,7 +181,7 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, uint32_t /*lane*/)
     return v;
 }
 
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v, uint32_t /*lane*/) {
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
     v = max(v, dpp_mov<0x111, 0xF>(v, 0u));
     v = max(v, dpp_mov<0x112, 0xF>(v, 0u));
     v = max(v, dpp_mov<0x114, 0xF>(v, 0u));
@@ -201,20 +201,39 @@ __device__ __forceinline__ uint32_t wave_incl_min(uint32_t v) {
     return v;
 }
 
-// sum of a u64 over the wave (DPP steps on both halves, 64-bit adds)
+// the wave's minimum / maximum, wave-uniform (the scan's last lane)
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+    return __builtin_amdgcn_readlane(wave_incl_min(v), kWave - 1);
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    return __builtin_amdgcn_readlane(wave_incl_max(v), kWave - 1);
+}
+
+// The DPP scan of a u64 sum, in place: per step moves on both halves and a 64-bit add. A macro,
+// so both functions below get the statements themselves (through a helper function, inlined,
+// the compiler split the adds and the kernels' code changed).
+#define CPK_SUM64_STEP(V, CTRL, ROWS)                                                           \
+    V += (uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)V, 0u) | ((uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)(V >> 32), 0u) << 32)
+#define CPK_SUM64_SCAN(V)          \
+    CPK_SUM64_STEP(V, 0x111, 0xF); \
+    CPK_SUM64_STEP(V, 0x112, 0xF); \
+    CPK_SUM64_STEP(V, 0x114, 0xF); \
+    CPK_SUM64_STEP(V, 0x118, 0xF); \
+    CPK_SUM64_STEP(V, 0x142, 0xA); \
+    CPK_SUM64_STEP(V, 0x143, 0xC)
+// inclusive sum of a u64 over the wave
+__device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t v) {
+    CPK_SUM64_SCAN(v);
+    return v;
+}
+// sum of a u64 over the wave, wave-uniform
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#define CPK_SUM64_STEP(CTRL, ROWS)                                                              \
-    v += (uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)v, 0u) | ((uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)(v >> 32), 0u) << 32)
-    CPK_SUM64_STEP(0x111, 0xF);
-    CPK_SUM64_STEP(0x112, 0xF);
-    CPK_SUM64_STEP(0x114, 0xF);
-    CPK_SUM64_STEP(0x118, 0xF);
-    CPK_SUM64_STEP(0x142, 0xA);
-    CPK_SUM64_STEP(0x143, 0xC);
-#undef CPK_SUM64_STEP
+    CPK_SUM64_SCAN(v);
     return (uint64_t)__builtin_amdgcn_readlane((uint32_t)v, kWave - 1) |
            ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), kWave - 1) << 32);
 }
+#undef CPK_SUM64_SCAN
+#undef CPK_SUM64_STEP
 
 // the previous lane's v (wave_shr:1); lane 0 gets ident
 __device__ __forceinline__ uint32_t wave_prev_lane(uint32_t v, uint32_t ident) { return dpp_mov<0x138, 0xF>(v, ident); }
@@ -242,10 +261,6 @@ __device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t l) {
 
 // Zero-byte tag of a little-endian word: bit k set <=> byte k != 0
 // (message.zig:257-262 builds the same tag byte-by-byte).
-__device__ __forceinline__ uint32_t nonzero_tag32(uint32_t x) {
-    uint32_t y = ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;   // byte high bit <=> byte != 0
-    return ((y & 0x80808080u) * 0x00204081u) >> 28;        // gather the 4 high bits
-}
 __device__ __forceinline__ uint32_t nonzero_tag(uint64_t w) {
     // byte k of c: bit 0 = byte k nonzero, bit 4 = byte k + 4 nonzero; the dot product with
     // 2^k gathers them (one full-rate v_dot4 instead of two quarter-rate multiplies)
@@ -302,13 +317,31 @@ constexpr SelLut make_compact_sel() {
 __device__ constexpr SelLut kCompactSel = make_compact_sel();
 __device__ __forceinline__ uint64_t expand_selector(uint32_t t) { return kExpandLut.v[t]; }
 
-// Unaligned 8-byte read from an LDS byte array (two aligned ds_read_b64 + funnel).
-__device__ __forceinline__ uint64_t lds_read_u64_unaligned(const uint8_t* base, uint32_t p) {
-    uint32_t a = p & ~7u;
-    uint64_t lo = *reinterpret_cast<const uint64_t*>(base + a);
-    uint64_t hi = *reinterpret_cast<const uint64_t*>(base + a + 8);
-    uint32_t sh = (p & 7u) * 8u;
-    return sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
+// Unaligned 8-byte read from an LDS byte array as two aligned ds_read_b64 and a branch-free
+// funnel shift (a byte-aligned ds_read_b64 is legal on gfx950 but measured ~2x slower in the
+// expand loop: the LDS splits it).
+__device__ __forceinline__ uint64_t lds_u64_at(const uint8_t* base, uint32_t p) {
+    const uint32_t a = p & ~7u;
+    const uint64_t lo = *reinterpret_cast<const uint64_t*>(base + a);
+    const uint64_t hi = *reinterpret_cast<const uint64_t*>(base + a + 8);
+    const uint32_t s = (p & 7u) * 8u;
+    return (lo >> s) | ((hi << 1) << (63u - s));
+}
+
+// 8-byte global loads: gload64 where p is known 8-aligned, ld_u64 / ld_u32 at any alignment
+// (gfx950 unaligned access: still one global_load_dwordx2 / dword).
+__device__ __forceinline__ uint64_t gload64(const uint8_t* p) {
+    return *reinterpret_cast<const uint64_t*>(p);
+}
+__device__ __forceinline__ uint64_t ld_u64(const uint8_t* p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
 }
 
 // Stage nch 16-B chunks from global g[0 .. 16*nch) into lds[0 .. 16*nch):
@@ -332,23 +365,6 @@ __device__ __forceinline__ void stage_linear(uint8_t* lds, const uint8_t* g, uin
     }
 }
 
-// expand: packed bytes d (byte r = r-th nonzero byte) -> word with zeros where tag bit is clear
-__device__ __forceinline__ uint64_t expand_word(uint64_t d, uint32_t t) {
-    const uint32_t s_lo = ((t & 0xFu) * 0x00204081u) & 0x01010101u;        // byte k = bit k
-    const uint32_t s_hi = (((t >> 4) & 0xFu) * 0x00204081u) & 0x01010101u;
-    const uint32_t inc_lo = s_lo * 0x01010101u;                             // inclusive byte prefix sums
-    const uint32_t inc_hi = s_hi * 0x01010101u + (inc_lo >> 24) * 0x01010101u;
-    const uint32_t m_lo = s_lo * 0xFFu, m_hi = s_hi * 0xFFu;
-    const uint32_t sel_lo = ((inc_lo - s_lo) & m_lo) | (0x0C0C0C0Cu & ~m_lo);
-    const uint32_t sel_hi = ((inc_hi - s_hi) & m_hi) | (0x0C0C0C0Cu & ~m_hi);
-    return perm64(d, (uint64_t)sel_lo | ((uint64_t)sel_hi << 32));
-}
-
-// ---------------------------------------------------------------------------
-// Serial per-wave fallback (lane 0), any unit size. Restates message.zig
-// directly over global memory. Used for units beyond the fast-path limits.
-// ---------------------------------------------------------------------------
-
 // Bytes [lo, hi) (0 <= lo < hi <= 16) of a 16-B chunk (x0 = bytes 0-7, x1 = bytes 8-15)
 // whose 16-B aligned home is c16: naturally aligned 1/2/4/8-B stores, up to 8-B alignment
 // and then down from it (at most 8 predicated stores). A byte loop runs to the wave's
@@ -371,10 +387,67 @@ __device__ __forceinline__ void store_partial16(uint8_t* c16, uint32_t lo, uint3
     if (lo + 2 <= hi) put(2);
     if (lo + 1 <= hi) put(1);
 }
-
-__device__ __forceinline__ uint64_t gload64(const uint8_t* p) {  // 8-aligned
-    return *reinterpret_cast<const uint64_t*>(p);
+// The same through global (address space 1) pointers, for kernels that count their LDS waits:
+// a generic pointer would make FLAT stores, which also count on lgkmcnt. (One template over the
+// pointer type changed the code of the kernels that use either, so both stay.)
+__device__ __forceinline__ void es_store_partial16(uint8_t* c16, uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1) {
+    typedef __attribute__((address_space(1))) uint8_t g8;
+    typedef __attribute__((address_space(1))) uint16_t g16;
+    typedef __attribute__((address_space(1))) uint32_t g32;
+    typedef __attribute__((address_space(1))) uint64_t g64;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(c16);
+    auto put = [&](uint32_t sz) {  // bytes [lo, lo + sz), lo aligned to sz
+        const uint64_t v = lo < 8 ? x0 >> (8 * lo) : x1 >> (8 * (lo - 8));
+        const uintptr_t p = base + lo;
+        if (sz == 8) *reinterpret_cast<g64*>(p) = v;
+        else if (sz == 4) *reinterpret_cast<g32*>(p) = (uint32_t)v;
+        else if (sz == 2) *reinterpret_cast<g16*>(p) = (uint16_t)v;
+        else *reinterpret_cast<g8*>(p) = (uint8_t)v;
+        lo += sz;
+    };
+    if ((lo & 1) && lo + 1 <= hi) put(1);
+    if ((lo & 2) && lo + 2 <= hi) put(2);
+    if ((lo & 4) && lo + 4 <= hi) put(4);
+    if (lo + 8 <= hi) put(8);
+    if (lo + 4 <= hi) put(4);
+    if (lo + 2 <= hi) put(2);
+    if (lo + 1 <= hi) put(1);
 }
+
+// s_waitcnt needs an immediate: wait until at most min(c, 8) / min(c, 63) vector-memory
+// operations are outstanding (a smaller count than the true number of younger operations only
+// waits longer). Two ladders: one function taking the cap compiled to different code in the
+// fill pass and the words decoder.
+__device__ __forceinline__ void vmcnt_at_most(uint32_t c) {
+    switch (c) {
+        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+        default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    }
+}
+__device__ __forceinline__ void vmcnt_at_most63(uint32_t c) {
+#define CPK_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+#define CPK_VM8(B) CPK_VM(B) CPK_VM(B + 1) CPK_VM(B + 2) CPK_VM(B + 3) CPK_VM(B + 4) CPK_VM(B + 5) CPK_VM(B + 6) CPK_VM(B + 7)
+    switch (c < 63u ? c : 63u) {
+        CPK_VM8(0) CPK_VM8(8) CPK_VM8(16) CPK_VM8(24) CPK_VM8(32) CPK_VM8(40) CPK_VM8(48)
+        CPK_VM(56) CPK_VM(57) CPK_VM(58) CPK_VM(59) CPK_VM(60) CPK_VM(61) CPK_VM(62)
+        default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
+    }
+#undef CPK_VM8
+#undef CPK_VM
+}
+
+// ---------------------------------------------------------------------------
+// Serial encoder (one lane), any unit size. Restates message.zig:200-271 directly
+// over global memory. Used for units beyond the fast-path limits.
+// ---------------------------------------------------------------------------
+
 __device__ __forceinline__ int word_has_zero_byte(uint64_t v) {  // message.zig:196-198
     return ((v - 0x0101010101010101ULL) & ~v & 0x8080808080808080ULL) != 0;
 }
@@ -419,57 +492,6 @@ __device__ uint64_t serial_pack(const uint8_t* in, uint64_t words, uint8_t* out)
         i += 1;
     }
     return o;
-}
-
-// message.zig:152-191; returns ST_OK / ST_EOF and the decoded size.
-__device__ int32_t serial_decoded_size(const uint8_t* p, uint64_t n, uint64_t* size) {
-    uint64_t i = 0, total = 0;
-    while (i < n) {
-        uint32_t t = p[i++];
-        if (t == 0x00) {
-            if (i >= n) return ST_EOF;
-            total += 8 * (1 + (uint64_t)p[i++]);
-        } else if (t == 0xFF) {
-            if (i + 8 > n) return ST_EOF;
-            i += 8;
-            if (i >= n) return ST_EOF;
-            uint64_t c = p[i++];
-            if (i + 8 * c > n) return ST_EOF;
-            total += 8 * (1 + c);
-            i += 8 * c;
-        } else {
-            uint32_t k = __popc(t);
-            if (i + k > n) return ST_EOF;
-            total += 8;
-            i += k;
-        }
-    }
-    *size = total;
-    return ST_OK;
-}
-
-// message.zig:97-142 (input already validated by serial_decoded_size).
-__device__ void serial_unpack(const uint8_t* p, uint64_t n, uint8_t* out) {
-    uint64_t i = 0, o = 0;
-    while (i < n) {
-        uint32_t t = p[i++];
-        if (t == 0x00) {
-            uint64_t z = 8 * (1 + (uint64_t)p[i++]);
-            for (uint64_t b = 0; b < z; ++b) out[o + b] = 0;
-            o += z;
-        } else if (t == 0xFF) {
-            for (int b = 0; b < 8; ++b) out[o + b] = p[i + b];
-            o += 8;
-            i += 8;
-            uint64_t c = p[i++];
-            for (uint64_t b = 0; b < 8 * c; ++b) out[o + b] = p[i + b];
-            o += 8 * c;
-            i += 8 * c;
-        } else {
-            for (int k = 0; k < 8; ++k) out[o + k] = ((t >> k) & 1u) ? p[i++] : 0;
-            o += 8;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -555,10 +577,6 @@ __device__ __forceinline__ void encode_stage(uint8_t* lds, const uint8_t* src, u
     encode_put(lds, v, (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15), words, lane);
 }
 
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-    return __builtin_amdgcn_readlane(wave_incl_min(v), kWave - 1);
-}
-
 // First Z break and first F break among words [0, nw) of src, nw <= 256, as
 // offsets (nw when there is none); wave-uniform results.
 __device__ __forceinline__ void encode_lookahead(const uint8_t* src, uint32_t nw, uint32_t lane, uint32_t& bz,
@@ -584,7 +602,7 @@ __device__ __forceinline__ void encode_lookahead(const uint8_t* src, uint32_t nw
 //
 // HOOK (encode_dense_kernel): a caller that learns the destination only from the tile's size.
 // hook->place(P, dst) runs once P is known, with the tile's words still in registers; it sets
-// dst and answers whether to write. NoTileHook: dst / room are the caller's, as ever.
+// dst and answers whether to write. NoTileHook: dst / room are the caller's.
 struct NoTileHook {};
 template <bool WRITE, bool SINGLE, bool FULL = false, class HOOK = NoTileHook>
 __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lut, uint32_t lane, uint32_t words,
@@ -659,8 +677,8 @@ __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lu
         scan = ((bz0 & (bz7 << 1)) | (bf0 & (bf7 << 1))) != 0;
     }
     if (scan) {
-        cz = wave_prev_lane(wave_incl_max(lbz, lane), 0u);
-        cf = wave_prev_lane(wave_incl_max(lbf, lane), 0u);
+        cz = wave_prev_lane(wave_incl_max(lbz), 0u);
+        cf = wave_prev_lane(wave_incl_max(lbf), 0u);
         // run end: the first break of the next lane that holds one (a lane's fb is its first
         // break, or the lookahead, which lies past every break of the tile): a ballot and one
         // shuffle instead of a six-step suffix-min scan
@@ -671,8 +689,8 @@ __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lu
     // carries for the next tile: the run starts open at the tile end
     uint32_t lz_all = 0, lf_all = 0;
     if (!SINGLE) {
-        lz_all = readlane(wave_incl_max(lbz, lane), 63);
-        lf_all = readlane(wave_incl_max(lbf, lane), 63);
+        lz_all = readlane(wave_incl_max(lbz), 63);
+        lf_all = readlane(wave_incl_max(lbf), 63);
     }
 
     uint32_t rs[8];  // run start of word t's class run (Z or F)
@@ -706,7 +724,7 @@ __device__ __forceinline__ uint32_t encode_tile(uint8_t* lds, const uint64_t* lu
         sz[t] = s;
         total += s;
     }
-    const uint32_t incl = wave_incl_sum(total, lane);
+    const uint32_t incl = wave_incl_sum(total);
     const uint32_t P = readlane(incl, 63);
     const uint32_t o = incl - total;
     cz_c = lz_all;
@@ -940,9 +958,6 @@ constexpr uint32_t kClassK = 12;        // per-block class counters (11 classes 
 __host__ __device__ inline uint64_t class_blocks(uint64_t n) { return (n + kClassBlock - 1) / kClassBlock; }
 // u32 index of the serial list (long units no tile / window table could hold)
 __host__ __device__ inline uint64_t serial_off(uint64_t n) { return kQHead + 3 * n + kClassK * class_blocks(n); }
-__device__ __forceinline__ bool decode_long_unit(const uint8_t* in, uint64_t in_off, uint64_t P, uint8_t* out,
-                                                 uint64_t out_off, uint64_t cap);
-
 // Units longer than one tile (encode_tiled_unit) that the tile table could not hold,
 // taken from the serial list and encoded one after another, tile by tile.
 template <bool WRITE>
@@ -1176,16 +1191,16 @@ __device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t
     // first Z / stretch break after the lane
     uint32_t cz = base, oi = base, pa = 0, ez = min(base + 8, wend), es = ez, lz_all = 0;
     if (scan_z) {
-        const uint32_t mz = wave_incl_max(lbz, lane);
+        const uint32_t mz = wave_incl_max(lbz);
         cz = wave_prev_lane(mz, 0u);
         ez = next_break(fbz != nbz, fbz, lane, nbz);
         if (lane == 0) cz = cz_c;
         lz_all = readlane(mz, 63);
     }
     if (scan_s) {
-        const uint32_t csx = wave_prev_lane(wave_incl_max(lbs, lane), 0u);
+        const uint32_t csx = wave_prev_lane(wave_incl_max(lbs), 0u);
         oi = csx ? csx : (ch_c ? ch_c - 1 : tb);
-        pa = max(wave_prev_lane(wave_incl_max(la, lane), 0u), ch_c);
+        pa = max(wave_prev_lane(wave_incl_max(la), 0u), ch_c);
         es = next_break(fbs != nbs, fbs, lane, nbs);
     }
 
@@ -1235,7 +1250,7 @@ __device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t
             org = ((smask >> t) & 1u) ? org : i + 1;
             par = ((amask >> t) & 1u) ? i + 1 : par;
         }
-        uint32_t run = max(seed, wave_prev_lane(wave_incl_max(lh, lane), 0u));
+        uint32_t run = max(seed, wave_prev_lane(wave_incl_max(lh), 0u));
         seed = 0;
         org = oi;
 #pragma unroll
@@ -1274,7 +1289,7 @@ __device__ __forceinline__ uint32_t encode_tile_cxx(uint8_t* lds, const uint64_t
     auto size_of = [&](int t) { return (szp >> (4 * t)) & 15u; };
     const uint32_t sz2 = (szp & 0x0F0F0F0Fu) + ((szp >> 4) & 0x0F0F0F0Fu);  // four sums of two, <= 20 each
     const uint32_t total = (sz2 * 0x01010101u) >> 24;
-    const uint32_t incl = wave_incl_sum(total, lane);
+    const uint32_t incl = wave_incl_sum(total);
     const uint32_t P = readlane(incl, 63);
     const uint32_t ob = incl - total;
     cz_c = lz_all;
@@ -1643,20 +1658,6 @@ __device__ __forceinline__ uint64_t dn_uniform64(uint64_t v, int l = -1) {
     const uint32_t uhi = l < 0 ? (uint32_t)__builtin_amdgcn_readfirstlane(hi) : (uint32_t)__builtin_amdgcn_readlane(hi, l);
     return (uint64_t)ulo | ((uint64_t)uhi << 32);
 }
-// inclusive sum of a u64 over the wave (wave_sum64's DPP steps)
-__device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t v) {
-#define CPK_SUM64_STEP(CTRL, ROWS)                                                              \
-    v += (uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)v, 0u) | ((uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)(v >> 32), 0u) << 32)
-    CPK_SUM64_STEP(0x111, 0xF);
-    CPK_SUM64_STEP(0x112, 0xF);
-    CPK_SUM64_STEP(0x114, 0xF);
-    CPK_SUM64_STEP(0x118, 0xF);
-    CPK_SUM64_STEP(0x142, 0xA);
-    CPK_SUM64_STEP(0x143, 0xC);
-#undef CPK_SUM64_STEP
-    return v;
-}
-
 __host__ __device__ inline uint64_t dense_tiles(uint64_t n) { return (n + kDnWaves - 1) / kDnWaves; }
 
 // Exclusive prefix of `tile` (> 0): the sum of every earlier tile's aggregate. All lanes of
@@ -2131,7 +2132,7 @@ __device__ __forceinline__ void msg_stage_pairs_map(const MsgView<1>& m, uint32_
         run = b ? b : run;
         v = (v & ~(0xFFull << (8 * k))) | ((uint64_t)run << (8 * k));
     }
-    const uint32_t before = wave_prev_lane(wave_incl_max(run, lane), 0u);  // marks increase with p
+    const uint32_t before = wave_prev_lane(wave_incl_max(run), 0u);  // marks increase with p
     uint64_t fill = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -2228,7 +2229,7 @@ __device__ __forceinline__ void encode_message_tile1_body(uint32_t msg, uint32_t
         return;
     }
     const uint32_t wl = (uint32_t)(len >> 3);
-    const uint32_t incl = wave_incl_sum(wl, lane);
+    const uint32_t incl = wave_incl_sum(wl);
     const uint32_t payload = readlane(incl, 63);
     const uint32_t hw = (1 + count + ((count & 1) ? 0 : 1)) / 2;  // toBytes 2135-2137, in words
     const uint32_t words = hw + payload;
@@ -2321,7 +2322,7 @@ __device__ __forceinline__ void encode_message_one(uint32_t msg, uint32_t lane, 
             wsum += wl[t];
         }
     }
-    const uint32_t incl = wave_incl_sum(wsum, lane);
+    const uint32_t incl = wave_incl_sum(wsum);
     uint32_t acc = incl - wsum;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -2512,31 +2513,20 @@ __global__ __launch_bounds__(kBlock) void message_init_kernel(const uint8_t* __r
 }
 
 // ---------------------------------------------------------------------------
-// DECODE, lane per unit
+// Decoded size, lane per unit: the size pass's fallback for units of kIxSizeMax (2 GiB) packed
+// bytes or more, which the size-only index walk declines (kStNeedFull; launch_decode)
 // ---------------------------------------------------------------------------
-// The record chain (tag -> record length) is inherently serial and speculative
-// chunk walks couple with it too slowly on packed data, so each
-// lane owns ONE unit and walks its chain exactly once, expanding every record as
-// it is found. The lane keeps a sliding window of its packed bytes in registers:
-// a 32-byte view (q0..q3) plus one 16-byte piece in flight (n0, n1). A CU holds
-// thousands of units in flight, which hides the memory latency of each lane's
-// dependent chain.
+// Each lane owns ONE unit and walks its record chain (tag -> record length) exactly once,
+// counting the words. The lane keeps a sliding window of its packed bytes in registers: a
+// 32-byte view (q0..q3) plus one 16-byte piece in flight (n0, n1).
 
-// View helpers take the window by value so the selects stay register selects
+// View helper takes the window by value so the selects stay register selects
 // (members selected through `this` were turned into an indexed alloca in LDS).
 __device__ __forceinline__ uint32_t view_byte(uint64_t q0, uint64_t q1, uint64_t q2, uint64_t q3, uint32_t o) {
     uint64_t a = (o & 8) ? q1 : q0;  // o < 32
     uint64_t b = (o & 8) ? q3 : q2;
     uint64_t q = (o & 16) ? b : a;
     return (uint32_t)(q >> (8 * (o & 7))) & 0xFFu;
-}
-__device__ __forceinline__ uint64_t view_word8(uint64_t q0, uint64_t q1, uint64_t q2, uint64_t q3, uint32_t o) {
-    // 8 bytes at view offset o, o <= 24
-    uint32_t i = o >> 3;
-    uint64_t lo = (i == 0) ? q0 : ((i == 1) ? q1 : q2);
-    uint64_t hi = (i == 0) ? q1 : ((i == 1) ? q2 : q3);
-    uint32_t sh = 8 * (o & 7);
-    return sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
 }
 __device__ __forceinline__ void load_piece(const uint8_t* base, uint32_t npieces, uint32_t idx, uint64_t& a,
                                            uint64_t& b) {
@@ -2550,37 +2540,20 @@ __device__ __forceinline__ void load_piece(const uint8_t* base, uint32_t npieces
     }
 }
 
-template <bool WRITE, bool CK = false>
-__global__ __launch_bounds__(kBlock) void decode_lane_kernel(const uint8_t* __restrict__ in,
-                                                             const uint64_t* __restrict__ in_off,
-                                                             const uint64_t* __restrict__ in_len,
-                                                             uint32_t n, uint8_t* __restrict__ out,
-                                                             const uint64_t* __restrict__ out_off,
-                                                             const uint64_t* __restrict__ out_cap,
-                                                             uint64_t* __restrict__ out_len,
-                                                             int32_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
-    if (WRITE) {
-        lut[threadIdx.x] = expand_selector(threadIdx.x);
-        __syncthreads();
-    }
+// out / out_off / out_cap are not read (the launcher passes the batch's arguments as they are).
+__global__ __launch_bounds__(kBlock) void decode_size_lane_kernel(const uint8_t* __restrict__ in,
+                                                                  const uint64_t* __restrict__ in_off,
+                                                                  const uint64_t* __restrict__ in_len,
+                                                                  uint32_t n, uint8_t* __restrict__ out,
+                                                                  const uint64_t* __restrict__ out_off,
+                                                                  const uint64_t* __restrict__ out_cap,
+                                                                  uint64_t* __restrict__ out_len,
+                                                                  int32_t* __restrict__ status) {
     const uint32_t unit = blockIdx.x * kBlock + threadIdx.x;
     if (unit >= n) return;
-    if (CK && status[unit] != kStNeedFull) return;  // size-only fallback after decode_index_kernel<true>
+    if (status[unit] != kStNeedFull) return;  // only the units decode_index_kernel<true> declined
     const uint8_t* src = in + in_off[unit];
     const uint64_t P = in_len[unit];
-    uint64_t* dst = nullptr;
-    uint64_t capw = 0;
-    if (WRITE) {
-        uint8_t* o = out + out_off[unit];
-        if (P > 0 && (reinterpret_cast<uintptr_t>(o) & 7)) {  // an empty unit writes nothing
-            out_len[unit] = 0;
-            status[unit] = ST_ARG;
-            return;
-        }
-        dst = reinterpret_cast<uint64_t*>(o);
-        capw = out_cap[unit] >> 3;
-    }
     const uint32_t s = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15);
     const uint64_t end64 = s + P;
     const uint8_t* base = src - s;
@@ -2601,10 +2574,6 @@ __global__ __launch_bounds__(kBlock) void decode_lane_kernel(const uint8_t* __re
     uint64_t pos = s;
     uint64_t wo = 0;
     int32_t st = ST_OK;
-    auto put = [&](uint64_t w) {
-        if (WRITE && wo < capw) dst[wo] = w;
-        ++wo;
-    };
     while (pos < end64) {
         ensure((uint32_t)pos);
         const uint32_t o = (uint32_t)pos - wb;
@@ -2612,25 +2581,23 @@ __global__ __launch_bounds__(kBlock) void decode_lane_kernel(const uint8_t* __re
         if (t == 0x00) {  // message.zig:101-110
             if (pos + 2 > end64) { st = ST_EOF; break; }
             const uint32_t c = view_byte(q0, q1, q2, q3, o + 1);
-            for (uint32_t k = 0; k <= c; ++k) put(0);
+            for (uint32_t k = 0; k <= c; ++k) ++wo;
             pos += 2;
         } else if (t == 0xFF) {  // message.zig:112-128
             if (pos + 10 > end64) { st = ST_EOF; break; }
-            const uint64_t w = view_word8(q0, q1, q2, q3, o + 1);
             const uint32_t c = view_byte(q0, q1, q2, q3, o + 9);
             if (pos + 10 + 8ULL * c > end64) { st = ST_EOF; break; }
-            put(w);
+            ++wo;
             pos += 10;
-            for (uint32_t k = 0; k < c; ++k) {
+            for (uint32_t k = 0; k < c; ++k) {  // the window follows the run (as the decoders read it)
                 ensure((uint32_t)pos);
-                put(view_word8(q0, q1, q2, q3, (uint32_t)pos - wb));
+                ++wo;
                 pos += 8;
             }
         } else {  // message.zig:131-141
             const uint32_t k = __popc(t);
             if (pos + 1 + k > end64) { st = ST_EOF; break; }
-            if (WRITE) put(perm64(view_word8(q0, q1, q2, q3, o + 1), lut[t]));
-            else put(0);
+            ++wo;
             pos += 1 + k;
         }
     }
@@ -2641,7 +2608,7 @@ __global__ __launch_bounds__(kBlock) void decode_lane_kernel(const uint8_t* __re
     }
     const uint64_t U = 8 * wo;
     out_len[unit] = U;
-    status[unit] = (WRITE && wo > capw) ? ST_SPACE : ST_OK;
+    status[unit] = ST_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -2733,24 +2700,6 @@ __device__ __forceinline__ uint32_t wv_walk(const uint8_t* pk, uint8_t* mk, uint
     hit = h;
     return r;
 }
-
-// Unaligned 8-byte LDS read as two aligned ds_read_b64 and a branch-free funnel
-// shift (a byte-aligned ds_read_b64 is legal on gfx950 but measured ~2x slower
-// in the expand loop: the LDS splits it).
-__device__ __forceinline__ uint64_t lds_u64_at(const uint8_t* base, uint32_t p) {
-    const uint32_t a = p & ~7u;
-    const uint64_t lo = *reinterpret_cast<const uint64_t*>(base + a);
-    const uint64_t hi = *reinterpret_cast<const uint64_t*>(base + a + 8);
-    const uint32_t s = (p & 7u) * 8u;
-    return (lo >> s) | ((hi << 1) << (63u - s));
-}
-// Unaligned 8-byte global read (gfx950 unaligned-buffer-access: one global_load_dwordx2).
-__device__ __forceinline__ uint64_t gload_u64_unaligned(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-
 
 // A window of a unit's packed bytes staged in the wave's LDS slice: window byte r (unit
 // byte X + r) at pk[sh + r] for r < nload. Records starting in [0, Pw) belong to the
@@ -2922,7 +2871,7 @@ __device__ __forceinline__ void wv_expand(const uint8_t* pk, uint8_t* mk, const 
                     const uint32_t t = lit ? 0xFFu : pk[sh + q];
                     word = perm64(lds_u64_at(pk, sh + q + 1), lut[t]);
                 } else {  // literal word past the staged bytes (long FF run), inside the input
-                    word = gload_u64_unaligned(w.g + q + 1);
+                    word = ld_u64(w.g + q + 1);
                 }
             }
             __builtin_nontemporal_store(word, o + i);  // streaming output (as the fill pass)
@@ -3004,7 +2953,7 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
                 break;
             }
             const uint32_t words = wv_count(pk, w.sh, ent, ce);
-            Wb += readlane(wave_incl_sum(words, lane), kWave - 1);
+            Wb += readlane(wave_incl_sum(words), kWave - 1);
             X += xw;
         }
         if (st != ST_OK || Wb > capw) {
@@ -3026,7 +2975,7 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
             break;
         }
         const uint32_t words = wv_count(pk, w.sh, ent, ce);
-        const uint32_t incl = wave_incl_sum(words, lane);
+        const uint32_t incl = wave_incl_sum(words);
         const uint32_t total = readlane(incl, kWave - 1);
         if (Wb + total > capw) fits = false;
         if (fits) wv_expand(pk, mk, lut, w, ent, ce, incl - words, incl, total, dst + Wb, lane);
@@ -3065,7 +3014,7 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
 // front of the slot (rec = nullptr).
 constexpr uint32_t kIxDead = 0xFFFFFFFFu;         // walk position of a lane with nothing (more) to walk
 constexpr uint32_t kFlPieces = 320;               // pass-2 window: 64 lanes x 5 pieces
-constexpr uint64_t kIxSizeMax = 1ull << 31;       // size-only walk: longer units use decode_lane_kernel
+constexpr uint64_t kIxSizeMax = 1ull << 31;       // size-only walk: longer units use decode_size_lane_kernel
 // record bytes per unit: 64 B per 8 rounds (+1 store) of at most kFlPieces * 16 B
 constexpr uint32_t kRecStride = 64 * ((kFlPieces * 16 / 64 + 8) / 8);
 static_assert(kRecStride == 704, "record region stride");
@@ -3109,7 +3058,7 @@ __device__ __forceinline__ bool decode_long_unit(const uint8_t* in, uint64_t in_
 //            (status kStNeedGate when it reached the framed length exactly);
 //   kRdGate  the write pass over in_len = consumed of the kStNeedGate units.
 // These take the messages of more than kRdWordsMax framed words; the words decoder takes the
-// rest (round 6; round 3's one-walk write pass, kRdOne, was removed with it).
+// rest.
 // A unit's status on entry says which pass owns it, so no pass redoes another's work.
 constexpr int kRdNone = 0, kRdWalk = 1, kRdGate = 2;
 
@@ -3366,23 +3315,6 @@ constexpr uint32_t kFlZero = 0xFFFFu;
 constexpr uint32_t kFlPos = 0x1FFFu;
 static_assert(kFlPk < kFlPos, "codes hold window positions");
 
-// s_waitcnt needs an immediate: wait until at most min(c, 8) vector-memory
-// operations are outstanding (a smaller count than the true number of younger
-// operations only waits longer).
-__device__ __forceinline__ void vmcnt_at_most(uint32_t c) {
-    switch (c) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    }
-}
-
 // Per-unit values the fill pass needs. A wave loads them for 64 of its units at
 // once (lane i: the wave's unit k0 + i), so one vector load per array serves 64
 // units and each unit reads its values from registers (readlane).
@@ -3422,7 +3354,7 @@ __device__ __forceinline__ void fl_bodies(const uint8_t* pk, uint16_t* code, uin
         const uint32_t ci = c[i];
         lh = ci != kFlZero ? ((8u * lane + i + 1u) << 16) | ci : lh;
     }
-    uint32_t h = fu_prev_lane(wave_incl_max(lh, lane));
+    uint32_t h = fu_prev_lane(wave_incl_max(lh));
     uint32_t body = 0;  // the FF head's count c (0: no body)
     if (h != 0 && !(h & kFlLit)) body = pk[h & kFlPos] == 0xFFu ? pk[(h & kFlPos) + 9] : 0u;
 #pragma unroll 1
@@ -3571,7 +3503,7 @@ __global__ __launch_bounds__(kFlWaves * kWave) void decode_fill_kernel(const uin
         const FillMeta nxt = meta(k1 & 63);  // st = -1 past the batch end
         load_unit(nxt);
         if (go) {
-            const uint32_t incl = wave_incl_sum(words, lane);
+            const uint32_t incl = wave_incl_sum(words);
             const uint32_t wbase = incl - words;
             const bool a16 = !(reinterpret_cast<uintptr_t>(cur.dst) & 15);
             uint64_t* const dst = reinterpret_cast<uint64_t*>(cur.dst);
@@ -3638,26 +3570,8 @@ __global__ __launch_bounds__(kFlWaves * kWave) void decode_fill_kernel(const uin
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// s_waitcnt needs an immediate: wait until at most min(c, 63) vector-memory operations are
-// outstanding (fewer than the true number of younger operations only waits longer).
-__device__ __forceinline__ void vmcnt_at_most63(uint32_t c) {
-#define CPK_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-#define CPK_VM8(B) CPK_VM(B) CPK_VM(B + 1) CPK_VM(B + 2) CPK_VM(B + 3) CPK_VM(B + 4) CPK_VM(B + 5) CPK_VM(B + 6) CPK_VM(B + 7)
-    switch (c < 63u ? c : 63u) {
-        CPK_VM8(0) CPK_VM8(8) CPK_VM8(16) CPK_VM8(24) CPK_VM8(32) CPK_VM8(40) CPK_VM8(48)
-        CPK_VM(56) CPK_VM(57) CPK_VM(58) CPK_VM(59) CPK_VM(60) CPK_VM(61) CPK_VM(62)
-        default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-    }
-#undef CPK_VM8
-#undef CPK_VM
-}
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    return __builtin_amdgcn_readlane(wave_incl_max(v, 0), kWave - 1);
-}
-
 // ---------------------------------------------------------------------------
-// Single-read decoder (round 5): lane per unit, one output word per step
+// DECODE, the words decoder (single read): lane per unit, one output word per step
 // ---------------------------------------------------------------------------
 // unpackPacked (message.zig:88-145) with the size pass's truncation checks (152-191) made on
 // the way. A wave owns 64 units. Their packed bytes stream through the index pass's ring
@@ -4178,7 +4092,7 @@ __global__ __launch_bounds__(1024) void class_scan_kernel(uint32_t* q, uint32_t 
 #pragma unroll
         for (uint32_t k = 0; k < kClassK; ++k) {
             v[k] = b < nb ? bl[b * kClassK + k] : 0u;
-            incl[k] = wave_incl_sum(v[k], lane);
+            incl[k] = wave_incl_sum(v[k]);
             if (lane == 63) wsum[w][k] = incl[k];
         }
         __syncthreads();
@@ -4247,7 +4161,7 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
     if (fused) {  // one block-wide inclusive scan per class: this block's exclusive prefix, the totals
 #pragma unroll
         for (uint32_t k = 0; k < kClassK; ++k) {
-            const uint32_t a = wave_incl_sum(v[k], lane);
+            const uint32_t a = wave_incl_sum(v[k]);
             if (lane == 63) wtot[w][k] = a;
             if (threadIdx.x == blockIdx.x) {
                 own_s[k] = v[k];
@@ -4330,7 +4244,7 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
     else q[kQHead + 2ull * n + (fused ? midb_s[c - CL_MID] : q[11 + (c - CL_MID)]) + idx] = u;
 }
 
-// ---- long units, tile-parallel encode ---------------------------------
+// ---- ENCODE, long units, tile-parallel --------------------------------
 // A long unit's tiles (512 words) are encoded by different waves, each like a mid unit
 // (encode_tile), instead of one wave walking the unit tile by tile:
 //   long_tiles_kernel  lists every tile of every long unit in a tile table (a unit's
@@ -4431,8 +4345,8 @@ __device__ __forceinline__ void encode_lookback(const uint8_t* src, uint32_t tb,
                 if (tg != 0xFF) bf = i + 1;
             }
         }
-        bz = readlane(wave_incl_max(bz, lane), kWave - 1);
-        bf = readlane(wave_incl_max(bf, lane), kWave - 1);
+        bz = readlane(wave_incl_max(bz), kWave - 1);
+        bf = readlane(wave_incl_max(bf), kWave - 1);
         if (!fz && bz) { lz = bz; fz = true; }
         if (!ff && bf) { lf = bf; ff = true; }
         end = w0;
@@ -4529,7 +4443,7 @@ __global__ __launch_bounds__(kBlock) void tile_encode_kernel(const uint8_t* __re
     }
 }
 
-// ---- long units, window-parallel decode ------------------------------
+// ---- DECODE, long units, window-parallel -----------------------------
 // A long unit's packed bytes are cut into windows of kWvWin bytes at fixed positions
 // X_j = j * kWvWin, and every window is a wave's work, instead of one wave walking the
 // unit window after window. Where the record chain enters window j is only known once
@@ -4630,7 +4544,7 @@ __global__ __launch_bounds__(kWvBlock) void window_spec_kernel(const uint8_t* __
         uint32_t ent, cs, ce;
         const uint32_t xw = wv_resolve(pk, mk, w, 0, lane, ent, cs, ce);
         const uint32_t words = wv_count(pk, w.sh, ent, ce);
-        const uint32_t incl = wave_incl_sum(words, lane);
+        const uint32_t incl = wave_incl_sum(words);
         const uint32_t total = readlane(incl, kWave - 1);
         // words before each verified record start of lanes 0 and 1 (window bytes [0, lim))
         const uint32_t lim = readlane(ce, 1);   // <= 2 * 73 bytes
@@ -4765,7 +4679,7 @@ __global__ __launch_bounds__(kWvBlock) void window_resolve_kernel(const uint8_t*
                             break;
                         }
                         const uint32_t wl = wv_count(pk, w.sh, ent, ce);
-                        words = readlane(wave_incl_sum(wl, lane), kWave - 1);
+                        words = readlane(wave_incl_sum(wl), kWave - 1);
                     }
                     if (lane == i) {
                         rent = d;
@@ -4820,17 +4734,17 @@ __global__ __launch_bounds__(kWvBlock) void window_fill_kernel(const uint8_t* __
         uint32_t ent, cs, ce;
         (void)wv_resolve(pk, mk, w, d, lane, ent, cs, ce);
         const uint32_t words = wv_count(pk, w.sh, ent, ce);
-        const uint32_t incl = wave_incl_sum(words, lane);
+        const uint32_t incl = wave_incl_sum(words);
         const uint32_t total = readlane(incl, kWave - 1);
         uint64_t* const dst = reinterpret_cast<uint64_t*>(out + out_off[unit]) + wb;
         wv_expand(pk, mk, lut, w, ent, ce, incl - words, incl, total, dst, lane);
     }
 }
 
-// ---- small units, streaming encoder (round 4) -----------------------------
+// ---- ENCODE, small units, streaming encoder ------------------------------
 // Lane per unit, 64 units per wave in lockstep rounds of 8 words: round k's 64-B blocks of
 // the wave's units come in by quad-coalesced 16-B loads issued a round ahead (only pieces
-// inside the unit, temporal: the lane-streaming kernel below re-fetched lines its lanes had
+// inside the unit, temporal: an earlier lane-streaming kernel re-fetched lines its lanes had
 // read, 4.2x its input; this one reads 3.6x, the neighbours of a unit's first and last lines
 // being other bins' units), land in the
 // units' 64-B LDS rings, and each lane codes its unit's 8 words with the Zig encoder's word
@@ -4854,31 +4768,6 @@ __device__ __forceinline__ void es_store16(uint8_t* p, uint64_t x0, uint64_t x1)
 __device__ __forceinline__ void es_store_byte(uint8_t* p, uint32_t v) {
     *reinterpret_cast<__attribute__((address_space(1))) uint8_t*>(reinterpret_cast<uintptr_t>(p)) = (uint8_t)v;
 }
-// bytes [lo, hi) of a 16-B chunk at c16 (x0 = bytes 0-7, x1 = 8-15), global stores
-__device__ __forceinline__ void es_store_partial16(uint8_t* c16, uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1) {
-    typedef __attribute__((address_space(1))) uint8_t g8;
-    typedef __attribute__((address_space(1))) uint16_t g16;
-    typedef __attribute__((address_space(1))) uint32_t g32;
-    typedef __attribute__((address_space(1))) uint64_t g64;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(c16);
-    auto put = [&](uint32_t sz) {  // bytes [lo, lo + sz), lo aligned to sz
-        const uint64_t v = lo < 8 ? x0 >> (8 * lo) : x1 >> (8 * (lo - 8));
-        const uintptr_t p = base + lo;
-        if (sz == 8) *reinterpret_cast<g64*>(p) = v;
-        else if (sz == 4) *reinterpret_cast<g32*>(p) = (uint32_t)v;
-        else if (sz == 2) *reinterpret_cast<g16*>(p) = (uint16_t)v;
-        else *reinterpret_cast<g8*>(p) = (uint8_t)v;
-        lo += sz;
-    };
-    if ((lo & 1) && lo + 1 <= hi) put(1);
-    if ((lo & 2) && lo + 2 <= hi) put(2);
-    if ((lo & 4) && lo + 4 <= hi) put(4);
-    if (lo + 8 <= hi) put(8);
-    if (lo + 4 <= hi) put(4);
-    if (lo + 2 <= hi) put(2);
-    if (lo + 1 <= hi) put(1);
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(kEsWaves * kWave) void encode_stream_kernel(
     const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint64_t* __restrict__ in_len,
@@ -5070,7 +4959,7 @@ __global__ __launch_bounds__(kEsWaves * kWave) void encode_stream_kernel(
 }
 
 
-// ---- small units, lane per unit ----------------------------------------------------------
+// ---- DECODE, small units, lane per unit ---------------------------------------------------
 // (a lane-per-unit encode_small_kernel, removed in round 5 (at 869fccf), measured C5 encode
 // 0.630 ms against the streaming encoder's 0.588-0.603, same box)
 // A persistent grid: each wave owns a contiguous range of the small list and its lanes
@@ -5446,8 +5335,8 @@ __global__ __launch_bounds__(kSgWaves * kWave) void decode_small_group_kernel(
             np = P ? (s + P + 15) >> 4 : 0u;
             capw = (uint32_t)(cap >> 3);
         }
-        const uint32_t ip = wave_incl_sum(valid ? np : 0u, lane);
-        const uint32_t iw = wave_incl_sum(valid ? capw : 0u, lane);
+        const uint32_t ip = wave_incl_sum(valid ? np : 0u);
+        const uint32_t iw = wave_incl_sum(valid ? capw : 0u);
         const bool fits = valid && 16u * ip <= kSgP && iw <= kSgW;  // prefix-monotone
         const uint32_t g = (uint32_t)__popcll(__ballot(fits));     // >= 1: one small unit always fits
         const bool mine = lane < g;
@@ -5522,7 +5411,7 @@ __global__ __launch_bounds__(kSgWaves * kWave) void decode_small_group_kernel(
         if (mine && st == ST_OK && wo > capw) st = ST_SPACE;
         // ---- 4. store the OK units' words, flattened by 16-B pairs -----------------------------
         const uint32_t npair = (mine && st == ST_OK) ? (wo + 1) >> 1 : 0u;
-        const uint32_t ipr = wave_incl_sum(npair, lane);
+        const uint32_t ipr = wave_incl_sum(npair);
         const uint32_t NPR = readlane(ipr, g - 1);
         opf[lane] = mine ? ipr - npair : 0xFFFFFFFFu;
         wave_lds_sync();  // step 3's output words and the pair prefix are visible
@@ -5605,16 +5494,6 @@ enum : uint32_t {
     VK_REQ_PTR,  // (no read) issue the read of the next pointer word
 };
 
-__device__ __forceinline__ uint64_t ld_u64(const uint8_t* p) {  // unaligned-safe 8-B load
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 __device__ __forceinline__ int64_t ptr_offset_words(uint64_t w) {  // message.zig:11-18
     const uint32_t raw = (uint32_t)((w >> 2) & 0x3FFFFFFFu);
     return (raw & 0x20000000u) ? (int64_t)raw - ((int64_t)1 << 30) : (int64_t)raw;
@@ -6049,7 +5928,7 @@ __device__ int32_t packed_header(const uint8_t* __restrict__ p, uint64_t P, uint
             c = p[r++];
         } else if (t == 0xFF) {  // :100-110
             if (P - r < 9) return ST_EOS;
-            w0 = gload_u64_unaligned(p + r);
+            w0 = ld_u64(p + r);
             c = p[r + 8];
             r += 9;
             if (P - r < 8ull * c) return ST_EOS;
@@ -6069,7 +5948,7 @@ __device__ int32_t packed_header(const uint8_t* __restrict__ p, uint64_t P, uint
         }
         if (t != 0x00) {
             for (uint64_t i = 0; i < nw && words + i < kHdrMaxWords; ++i) {
-                const uint64_t w = i == 0 ? w0 : gload_u64_unaligned(lit + 8 * (i - 1));
+                const uint64_t w = i == 0 ? w0 : ld_u64(lit + 8 * (i - 1));
                 const uint64_t j = 2 * (words + i);
                 if (j >= 1 && j <= count) total += (uint32_t)w;
                 if (j + 1 <= count) total += w >> 32;
@@ -6243,7 +6122,7 @@ __global__ __launch_bounds__(kWvBlock) void frame_walk_kernel(const uint8_t* __r
                     words += 1u + ((t == 0u) ? b1 : 0u) + ((t == 0xFFu) ? c9 : 0u);
                     r += len;
                 }
-                const uint32_t incl = wave_incl_sum(words, lane);
+                const uint32_t incl = wave_incl_sum(words);
                 const uint32_t total = readlane(incl, kWave - 1);
                 if (wd + total >= Lw) {  // the message ends in this window
                     const uint64_t bm = __ballot(wd + incl >= Lw);
@@ -6406,12 +6285,9 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(uint64_t* __restrict__ 
         if (base + k < n) off[base + k] += add;
 }
 
-}  // namespace cpk
-
 // ---------------------------------------------------------------------------
 // launchers (kernels.h)
 // ---------------------------------------------------------------------------
-namespace cpk {
 
 static inline uint32_t blocks_for(uint32_t n) { return (n + kWavesPerBlock - 1) / kWavesPerBlock; }
 
@@ -6485,20 +6361,12 @@ static uint32_t resident_blocks(K kernel, int block, uint32_t fallback_per_cu) {
     return (uint32_t)(cus * per);
 }
 
-static bool class_scan_launched();  // CAPNP_PACKED_LAUNCH_CLASS_SCAN (below)
-
-// Class the batch's units (class_count / class_scan / class_scatter) on the caller's stream.
-template <int KIND>
-static void launch_classes(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
-                           uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t* q,
-                           int32_t* status, hipStream_t stream, uint32_t words_min = ~0u) {
-    const uint32_t nb = (n + kClassBlock - 1) / kClassBlock;
-    // up to kClassBlock class blocks (1M units), the scatter does the scan itself
-    const uint32_t fused = nb >= 1 && nb <= kClassBlock && !class_scan_launched() ? 1u : 0u;
-    class_count_kernel<KIND><<<nb, kClassBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, q, status);
-    if (!fused) class_scan_kernel<<<1, 1024, 0, stream>>>(q, n, nb, words_min);
-    class_scatter_kernel<KIND><<<nb, kClassBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, q, fused,
-                                                               words_min);
+// f(std::true_type{}) or f(std::false_type{}): a launcher names its kernels' bool template
+// arguments (WRITE, CXX) once, in a generic lambda, instead of once per value.
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // Launch policy (capnp_packed_set_launch_flags, process-wide; no result depends on it):
@@ -6516,6 +6384,20 @@ static std::atomic<uint32_t> g_launch_flags{0};
 uint32_t set_launch_flags(uint32_t f) { return g_launch_flags.exchange(f); }
 static bool mid_side_stream() { return g_launch_flags.load(std::memory_order_relaxed) & CAPNP_PACKED_LAUNCH_MID_SIDE_STREAM; }
 static bool class_scan_launched() { return g_launch_flags.load(std::memory_order_relaxed) & CAPNP_PACKED_LAUNCH_CLASS_SCAN; }
+
+// Class the batch's units (class_count / class_scan / class_scatter) on the caller's stream.
+template <int KIND>
+static void launch_classes(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                           uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t* q,
+                           int32_t* status, hipStream_t stream, uint32_t words_min = ~0u) {
+    const uint32_t nb = (n + kClassBlock - 1) / kClassBlock;
+    // up to kClassBlock class blocks (1M units), the scatter does the scan itself
+    const uint32_t fused = nb >= 1 && nb <= kClassBlock && !class_scan_launched() ? 1u : 0u;
+    class_count_kernel<KIND><<<nb, kClassBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, q, status);
+    if (!fused) class_scan_kernel<<<1, 1024, 0, stream>>>(q, n, nb, words_min);
+    class_scatter_kernel<KIND><<<nb, kClassBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, q, fused,
+                                                               words_min);
+}
 
 class SideLaunch {
   public:
@@ -6713,37 +6595,23 @@ hipError_t launch_encode(const uint8_t* in, const uint64_t* in_off, const uint64
     // mid units on a second side stream beside the small-unit kernel (LAUNCH_MID_SIDE_STREAM)
     const hipStream_t ms = mid_side_stream() ? side.stream2() : stream;
     long_tiles_kernel<<<list_blocks(n), 256, 0, ss>>>(in_len, n, q);
-    if (write) {
-        tile_encode_kernel<kTilesSize, true><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off,
-                                                                             out_cap, out_len, status, q);
-        tile_encode_kernel<kTilesWrite, true><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off,
-                                                                              out_cap, out_len, status, q);
-        encode_tiled_kernel<true><<<tiled_blocks, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                    out_len, status, q);
+    with_bool(write, [&](auto w) {
+        constexpr bool W = decltype(w)::value;
+        tile_encode_kernel<kTilesSize, W><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                          out_len, status, q);
+        tile_encode_kernel<kTilesWrite, W><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                           out_len, status, q);
+        encode_tiled_kernel<W><<<tiled_blocks, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                                 status, q);
         if (ms != stream)  // LAUNCH_MID_SIDE_STREAM: the mid units beside the small ones
-            encode_kernel<true><<<mid_blocks, kBlock, 0, ms>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
-                                                                status, mid, mid_count);
-        encode_stream_kernel<true><<<es_blocks, kEsWaves * kWave, 0, stream>>>(in, in_off, in_len, n, out, out_off,
-                                                                               out_cap, out_len, status, q);
+            encode_kernel<W><<<mid_blocks, kBlock, 0, ms>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                             status, mid, mid_count);
+        encode_stream_kernel<W><<<es_blocks, kEsWaves * kWave, 0, stream>>>(in, in_off, in_len, n, out, out_off,
+                                                                            out_cap, out_len, status, q);
         if (ms == stream)
-            encode_kernel<true><<<mid_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                    out_len, status, mid, mid_count);
-    } else {
-        tile_encode_kernel<kTilesSize, false><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off,
-                                                                              out_cap, out_len, status, q);
-        tile_encode_kernel<kTilesWrite, false><<<tiles_res, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off,
-                                                                               out_cap, out_len, status, q);
-        encode_tiled_kernel<false><<<tiled_blocks, kBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                     out_len, status, q);
-        if (ms != stream)
-            encode_kernel<false><<<mid_blocks, kBlock, 0, ms>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                 out_len, status, mid, mid_count);
-        encode_stream_kernel<false><<<es_blocks, kEsWaves * kWave, 0, stream>>>(in, in_off, in_len, n, out, out_off,
-                                                                                out_cap, out_len, status, q);
-        if (ms == stream)
-            encode_kernel<false><<<mid_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                     out_len, status, mid, mid_count);
-    }
+            encode_kernel<W><<<mid_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                                 status, mid, mid_count);
+    });
     e = hipGetLastError();
     const hipError_t j = side.join();
     return e != hipSuccess ? e : j;
@@ -6753,27 +6621,9 @@ hipError_t launch_encode(const uint8_t* in, const uint64_t* in_off, const uint64
 // (hipOccupancy..., LDS/VGPR-bound), each wave striding over the batch with one
 // unit in flight ahead.
 static uint32_t fill_blocks(uint32_t n) {
-    static const uint32_t resident = [] {  // thread-safe one-time init (C++11 static)
-        int dev = 0, cus = 0, per = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, decode_fill_kernel, kFlWaves * kWave, 0) !=
-                hipSuccess || per <= 0)
-            per = 4;
-        return (uint32_t)(cus * per);
-    }();
+    static const uint32_t resident = resident_blocks(decode_fill_kernel, kFlWaves * kWave, 4);
     const uint32_t full = (n + kFlWaves - 1) / kFlWaves;
     return full < resident ? full : resident;
-}
-
-// Pass 1 of the indexed decoder: one wave (64 units) per block.
-template <bool SIZE_ONLY>
-static void launch_index(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* out,
-                         const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
-                         hipStream_t stream) {
-    decode_index_kernel<SIZE_ONLY><<<ix_blocks_for(n), kWave * kIxBw, 0, stream>>>(in, in_off, in_len, n, out, out_off,
-                                                                                   out_cap, out_len, status, nullptr);
 }
 
 // Grid of the fallback pass for units a first pass declined: it strides over the
@@ -6831,7 +6681,7 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
         const hipError_t j = side.join();
         if (e == hipSuccess) e = j;
         if (e != hipSuccess) return e;
-        decode_lane_kernel<false, true><<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(
+        decode_size_lane_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(
             in, in_off, in_len, n, out, out_off, out_cap, out_len, status);
         return hipGetLastError();
     }
@@ -6873,9 +6723,9 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
     decode_wave_kernel<kWvLong><<<long_blocks, kWvBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
                                                                    out_len, status, q);
     const uint32_t* const mid = q + kQHead + 2ull * n;
-    // the mid units' passes on a second side stream, before the small kernel (mid_side_stream)
-    const hipStream_t ms = mid_stream ? side.stream2() : stream;
-    if (!mid_stream) {
+    // the small units' kernel: on the caller's stream, before the mid units' passes or, when those
+    // go on a second side stream (mid_side_stream), after their launches
+    const auto launch_small = [&] {
         if (small_variant() == 0) {
             static const uint32_t sg_res = resident_blocks(decode_small_group_kernel, kSgWaves * kWave, 3);
             decode_small_group_kernel<<<std::min((n + kSgWaves * kWave - 1) / (kSgWaves * kWave), sg_res),
@@ -6885,9 +6735,12 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
             decode_small_kernel<<<sm_blocks, kSmBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
                                                                      out_len, status, q);
         }
-    }
-    // mid units: the indexed two-pass decoder (index pass + fill pass), the single-read words
-    // decoder, or in a dev build the fused single-pass decoder (capnp_packed_set_decoder)
+    };
+    // the mid units' passes on a second side stream, before the small kernel (mid_side_stream)
+    const hipStream_t ms = mid_stream ? side.stream2() : stream;
+    if (!mid_stream) launch_small();
+    // mid units: the indexed two-pass decoder (index pass + fill pass) and, where it pays, the
+    // single-read words decoder (capnp_packed_set_decoder)
     if (words) {  // [0, q[20]) two-pass, [q[20], q[4]) words (either may be empty)
         const uint32_t lw_blocks = (n + kLwWaves * kWave - 1) / (kLwWaves * kWave);
         uint8_t* const rec = reinterpret_cast<uint8_t*>(q) + rec_region_off(n);
@@ -6902,25 +6755,14 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
         // usually none: the kernel returns at once)
         decode_wave_kernel<kWvMarked><<<fallback_blocks(n), kWvBlock, 0, ms>>>(in, in_off, in_len, n, out, out_off,
                                                                             out_cap, out_len, status, q + 21);
-    } else
-    {
+    } else {
         uint8_t* const rec = reinterpret_cast<uint8_t*>(q) + rec_region_off(n);  // piece records, off the output slots
         decode_index_kernel<false><<<ix_blocks_for(n), kWave * kIxBw, 0, ms>>>(
             in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mid, q + 4, rec);
         decode_fill_kernel<<<fill_blocks(n), kFlWaves * kWave, 0, ms>>>(in, in_off, in_len, n, out, out_off,
                                                                            out_len, out_cap, status, mid, q + 4, rec);
     }
-    if (mid_stream) {
-        if (small_variant() == 0) {
-            static const uint32_t sg_res = resident_blocks(decode_small_group_kernel, kSgWaves * kWave, 3);
-            decode_small_group_kernel<<<std::min((n + kSgWaves * kWave - 1) / (kSgWaves * kWave), sg_res),
-                                        kSgWaves * kWave, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                       out_len, status, q);
-        } else {
-            decode_small_kernel<<<sm_blocks, kSmBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                     out_len, status, q);
-        }
-    }
+    if (mid_stream) launch_small();
     e = hipGetLastError();
     const hipError_t j = side.join();
     return e != hipSuccess ? e : j;
@@ -6933,17 +6775,13 @@ hipError_t launch_encode_message(const uint64_t* seg_ptr, const uint64_t* seg_le
     if (n == 0) return hipSuccess;
     // every message, then the marked multi-tile ones (a grid striding over the statuses)
     const uint32_t tiled_blocks = min(((n + kWave - 1) / kWave + kWavesPerBlock - 1) / kWavesPerBlock, 2048u);
-    if (write) {
-        encode_message_kernel<true, false><<<blocks_for((n + 1) / 2), kBlock, 0, stream>>>(
-                seg_ptr, seg_len, seg_first, seg_count, n, out, out_off, out_cap, out_len, status);
-        encode_message_kernel<true, true><<<tiled_blocks, kBlock, 0, stream>>>(
+    with_bool(write, [&](auto w) {
+        constexpr bool W = decltype(w)::value;
+        encode_message_kernel<W, false><<<blocks_for((n + 1) / 2), kBlock, 0, stream>>>(
             seg_ptr, seg_len, seg_first, seg_count, n, out, out_off, out_cap, out_len, status);
-    } else {
-        encode_message_kernel<false, false><<<blocks_for((n + 1) / 2), kBlock, 0, stream>>>(
-                seg_ptr, seg_len, seg_first, seg_count, n, out, out_off, out_cap, out_len, status);
-        encode_message_kernel<false, true><<<tiled_blocks, kBlock, 0, stream>>>(
+        encode_message_kernel<W, true><<<tiled_blocks, kBlock, 0, stream>>>(
             seg_ptr, seg_len, seg_first, seg_count, n, out, out_off, out_cap, out_len, status);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -6971,12 +6809,10 @@ hipError_t launch_decode_one(const uint8_t* in, const uint64_t* in_off, const ui
 hipError_t launch_encode_one(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out,
                              const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
                              bool write, hipStream_t stream) {
-    if (write)
-        encode_kernel<true><<<1, kBlock, 0, stream>>>(in, in_off, in_len, 1, out, out_off, out_cap, out_len, status,
-                                                        nullptr, nullptr);
-    else
-        encode_kernel<false><<<1, kBlock, 0, stream>>>(in, in_off, in_len, 1, out, out_off, out_cap, out_len, status,
-                                                         nullptr, nullptr);
+    with_bool(write, [&](auto w) {
+        encode_kernel<decltype(w)::value><<<1, kBlock, 0, stream>>>(in, in_off, in_len, 1, out, out_off, out_cap,
+                                                                     out_len, status, nullptr, nullptr);
+    });
     return hipGetLastError();
 }
 
@@ -6989,17 +6825,13 @@ hipError_t launch_encode_cxx(const uint8_t* in, const uint64_t* in_off, const ui
     const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
     // the units of more than one tile: a grid striding over the lengths, 64 per wave and load
     const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
-    if (write) {
-        encode_cxx_kernel<true><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
-                                                               status);
-        encode_cxx_long_kernel<true><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                         out_len, status);
-    } else {
-        encode_cxx_kernel<false><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
-                                                                status);
-        encode_cxx_long_kernel<false><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off,
-                                                                          out_cap, out_len, status);
-    }
+    with_bool(write, [&](auto w) {
+        constexpr bool W = decltype(w)::value;
+        encode_cxx_kernel<W><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
+                                                            status);
+        encode_cxx_long_kernel<W><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                      out_len, status);
+    });
     return hipGetLastError();
 }
 
@@ -7009,12 +6841,10 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
                                      hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (write)
-        encode_message_cxx_kernel<true><<<blocks, kBlock, 0, stream>>>(seg_ptr, seg_len, seg_first, seg_count, n, out,
-                                                                       out_off, out_cap, out_len, status);
-    else
-        encode_message_cxx_kernel<false><<<blocks, kBlock, 0, stream>>>(seg_ptr, seg_len, seg_first, seg_count, n, out,
-                                                                        out_off, out_cap, out_len, status);
+    with_bool(write, [&](auto w) {
+        encode_message_cxx_kernel<decltype(w)::value><<<blocks, kBlock, 0, stream>>>(
+            seg_ptr, seg_len, seg_first, seg_count, n, out, out_off, out_cap, out_len, status);
+    });
     return hipGetLastError();
 }
 
@@ -7036,32 +6866,23 @@ hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const 
         return hipGetLastError();
     }
     const uint32_t blocks = (uint32_t)dense_tiles(n);
-    uint64_t* const w = static_cast<uint64_t*>(ws);
-#define CPK_DENSE(W, C)                                                                                          \
-    encode_dense_kernel<W, C><<<blocks, kDnBlock, 0, stream>>>(in, in_off, in_len, n, out, out_base, out_cap, \
-                                                               out_off, out_len, status, w)
+    uint64_t* const w64 = static_cast<uint64_t*>(ws);
     // the units of more than one tile: their sizes before, their bytes after (no such unit: one
     // pass over the lengths each)
     const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
-#define CPK_DENSE_LONG(W, C)                                                                                     \
-    encode_dense_long_kernel<W, C><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_len, \
-                                                                       status, w, dense_workspace_bytes(n) / 8)
-    if (cxx) CPK_DENSE_LONG(false, true);
-    else CPK_DENSE_LONG(false, false);
-    if (out) {
-        if (cxx) {
-            CPK_DENSE(true, true);
-            CPK_DENSE_LONG(true, true);
-        } else {
-            CPK_DENSE(true, false);
-            CPK_DENSE_LONG(true, false);
-        }
-    } else {
-        if (cxx) CPK_DENSE(false, true);
-        else CPK_DENSE(false, false);
-    }
-#undef CPK_DENSE_LONG
-#undef CPK_DENSE
+    with_bool(cxx, [&](auto c) {
+        constexpr bool C = decltype(c)::value;
+        const auto dense_long = [&](auto w) {
+            encode_dense_long_kernel<decltype(w)::value, C><<<long_blocks, kBlock, 0, stream>>>(
+                in, in_off, in_len, n, out, out_off, out_len, status, w64, dense_workspace_bytes(n) / 8);
+        };
+        dense_long(std::false_type{});
+        with_bool(out != nullptr, [&](auto w) {
+            encode_dense_kernel<decltype(w)::value, C><<<blocks, kDnBlock, 0, stream>>>(
+                in, in_off, in_len, n, out, out_base, out_cap, out_off, out_len, status, w64);
+        });
+        if (out) dense_long(std::true_type{});
+    });
     return hipGetLastError();
 }
 
@@ -7146,15 +6967,7 @@ hipError_t launch_validate(const uint8_t* in, const uint64_t* in_off, const uint
                            uint64_t* words, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     // persistent grid: the resident waves, each owning a contiguous range of messages
-    static const uint32_t resident = [] {  // thread-safe one-time init (C++11 static)
-        int dev = 0, cus = 0, per = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, validate_kernel<false>, kWave, 0) != hipSuccess || per <= 0)
-            per = 8;
-        return (uint32_t)(cus * per);
-    }();
+    static const uint32_t resident = resident_blocks(validate_kernel<false>, kWave, 8);
     const uint32_t full = (n + kWave - 1) / kWave;
     const uint32_t blocks = full < resident ? full : resident;
     const uint32_t per_wave = (uint32_t)(((uint64_t)n + blocks - 1) / blocks);
@@ -7226,6 +7039,3 @@ hipError_t launch_scan(const uint64_t* len, uint32_t n, uint64_t base, uint64_t*
 }
 
 }  // namespace cpk
-
-// Diagnostic builds only: read and clear the phase cycle sums.
-
