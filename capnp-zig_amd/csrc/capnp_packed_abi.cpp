@@ -6,6 +6,16 @@
 // mutex-guarded device context; batch calls only enqueue kernels on the
 // caller's stream. There is no CPU code path: without a gfx950 device every
 // compute entry point returns CAPNP_PACKED_NO_DEVICE.
+//
+// How the file is laid out:
+// - Buf is the one owner of device and page-locked memory. How a buffer grows (Growth) is data
+//   of its call site; freeing is an explicit release(), never a destructor.
+// - Every device scratch block has one definition that sizes it and hands out its typed parts
+//   (UnitCols and its three blocks, StateBlock, RoundBlock, SpecBlock): reserve calls, copies
+//   and launch arguments all take them from there.
+// - The framer session's read (framer_read_locked) is a loop over named steps (append,
+//   walk_pass, decode_pass, commit_pass); where its bytes live is planned in framer_layout.h,
+//   which knows no HIP.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +28,7 @@
 #include <vector>
 
 #include "capnp_packed.h"
+#include "framer_layout.h"
 #include "kernels.h"
 
 namespace {
@@ -32,6 +43,9 @@ int fail(int status, const std::string& msg) {
 int hip_fail(hipError_t e, const char* what) {
     return fail(CAPNP_PACKED_DEVICE_ERROR, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// What a launcher or a chain of HIP calls returned, as a status.
+int launched(hipError_t e, const char* what) { return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, what); }
 
 std::once_flag g_init_once;
 int g_init_status = CAPNP_PACKED_NO_DEVICE;
@@ -68,61 +82,191 @@ int ensure_device() {
     return CAPNP_PACKED_OK;
 }
 
-// Device context for the single-buffer host entry points: grow-only device buffers and
-// pinned host staging (the caller's pageable bytes are copied into pinned memory, so the
-// H2D / D2H copies run as DMA at full PCIe rate), one stream, the meta block's host copy
-// in pinned memory too.
+// ---------------------------------------------------------------------------
+// Buffers
+// ---------------------------------------------------------------------------
+// How a buffer grows: the bytes to allocate for a call that needs `need`, the label of a failed
+// allocation, and whether a buffer grown by an unusually large call is given back on the next
+// call that needs a quarter of it or less (above 64 MiB), so that its owner does not pin its
+// peak for the process.
+struct Growth {
+    const char* what;
+    uint64_t (*want)(uint64_t need);
+    bool give_back;
+};
+uint64_t half_more_from_64k(uint64_t need) { return need < 65536 ? 65536 : need + need / 2; }
+uint64_t half_more_min_4k(uint64_t need) { return std::max<uint64_t>(need + need / 2, 4096); }
+uint64_t quarter_more_min_1m(uint64_t need) { return std::max<uint64_t>(need + need / 4, 1u << 20); }
+uint64_t exactly(uint64_t need) { return need; }
+
+constexpr Growth kSingleDevice{"hipMalloc(workspace)", half_more_from_64k, true};       // single-buffer calls
+constexpr Growth kSingleStaging{"hipHostMalloc(staging)", half_more_from_64k, true};
+constexpr Growth kFrameRounds{"hipMalloc(framer)", half_more_from_64k, false};          // frame_connections
+constexpr Growth kSession{"hipMalloc(framer session)", half_more_from_64k, false};      // the framer session
+constexpr Growth kSessionArena{"hipMalloc(framer arena)", exactly, false};
+constexpr Growth kSessionMeta{"hipHostMalloc(framer metadata)", half_more_min_4k, false};
+constexpr Growth kSessionStaging{"hipHostMalloc(framer staging)", quarter_more_min_1m, false};
+
+// A device (hipMalloc) or page-locked host (hipHostMalloc) allocation and its size. reserve()
+// keeps what holds `need` bytes and otherwise replaces it (the contents are not kept).
+// There is no destructor: the process-lifetime contexts below (g_ctx, g_fr) never free, because
+// at static destruction the HIP runtime may already be gone; every other owner calls release().
+template <bool Pinned>
+struct Buf {
+    uint8_t* p = nullptr;
+    uint64_t cap = 0;
+
+    int reserve(uint64_t need, const Growth& g) {
+        if (p && need <= cap && !(g.give_back && cap > (64u << 20) && need <= cap / 4)) return CAPNP_PACKED_OK;
+        if (need > (SIZE_MAX / 3) * 2)  // g.want(need) stays inside size_t
+            return fail(CAPNP_PACKED_OUT_OF_SPACE,
+                        Pinned ? "staging size overflows size_t" : "workspace size overflows size_t");
+        release();
+        const uint64_t want = g.want(need);
+        const hipError_t e = Pinned ? hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault)
+                                    : hipMalloc(reinterpret_cast<void**>(&p), want);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return hip_fail(e, g.what);
+        }
+        cap = want;
+        return CAPNP_PACKED_OK;
+    }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Scratch layouts. Each is a view (base pointer and counts) of a block on the device or of its
+// host copy; the byte layout is the same on both sides.
+// ---------------------------------------------------------------------------
+// The metadata of n units, column after column (one u64 per unit each). Every block starts with
+// the kernels' four inputs and out_len; the columns after them differ per block.
+struct UnitCols {
+    uint64_t* p;
+    uint64_t n;
+    uint64_t* col(uint32_t i) const { return p + i * n; }
+    int32_t* col32(uint32_t i) const { return reinterpret_cast<int32_t*>(col(i)); }  // i32 in a u64 column
+    uint64_t* in_off() const { return col(0); }
+    uint64_t* in_len() const { return col(1); }
+    uint64_t* out_off() const { return col(2); }
+    uint64_t* out_cap() const { return col(3); }
+    uint64_t* out_len() const { return col(4); }
+    uint64_t inputs_bytes() const { return 4 * n * 8; }  // in_off .. out_cap: one H2D
+};
+// run_single's one unit: then status, consumed. The whole block crosses both ways.
+struct SingleMeta : UnitCols {
+    static constexpr uint64_t kBytes = 7 * 8, kAllocBytes = 8 * 8;
+    explicit SingleMeta(uint64_t* base) : UnitCols{base, 1} {}
+    int32_t* status() const { return col32(5); }
+    uint64_t* consumed() const { return col(6); }
+};
+// A round of capnp_packed_frame_connections: then consumed, status.
+struct RoundMeta : UnitCols {
+    static uint64_t bytes(uint64_t n) { return 7 * n * 8; }
+    uint64_t* consumed() const { return col(5); }
+    int32_t* status() const { return col32(6); }
+    uint64_t results_bytes() const { return 2 * n * 8 + n * 4; }  // out_len, consumed, status: one D2H
+};
+// A decode pass of the framer session: then status.
+struct UnitBlock : UnitCols {
+    static uint64_t host_bytes(uint64_t n) { return 6 * n * 8; }
+    static uint64_t device_bytes(uint64_t n) { return host_bytes(n) + 64; }
+    int32_t* status() const { return col32(5); }
+    uint64_t results_bytes() const { return 2 * n * 8; }  // out_len and the status column: one D2H
+};
+
+// The framer session's state block: seven columns of n entries (u64 base, avail, need, X, W and
+// a free slot; i32 status in the seventh).
+// On the device a read's copy jobs live past the columns in the same allocation, and the jobs
+// that append() enqueues without waiting are still being read when the read's first walk pass
+// reserves the block for its columns. That reserve must not reallocate it. Both sizes come from
+// device_bytes(): the pass asks for device_bytes(n, 0), never more than the device_bytes(n, jobs)
+// the append asked for, and the buffer only grows.
+// The host copy (page-locked) holds the pass's list (u32 per connection) past the columns.
+struct StateBlock {
+    uint8_t* p;
+    uint64_t n;
+    static uint64_t cols_bytes(uint64_t n) { return n * 56; }
+    static uint64_t jobs_at(uint64_t n) { return cols_bytes(n) + 256; }
+    static uint64_t device_bytes(uint64_t n, uint64_t job_bytes) { return jobs_at(n) + job_bytes + 64 * n + 4096; }
+    static uint64_t host_bytes(uint64_t n) { return cols_bytes(n) + 4 * n; }
+    uint64_t* col(uint32_t i) const { return reinterpret_cast<uint64_t*>(p) + i * n; }
+    uint64_t* base() const { return col(0); }
+    uint64_t* avail() const { return col(1); }
+    uint64_t* need() const { return col(2); }
+    uint64_t* X() const { return col(3); }
+    uint64_t* W() const { return col(4); }
+    int32_t* status() const { return reinterpret_cast<int32_t*>(col(6)); }
+    uint64_t* jobs() const { return reinterpret_cast<uint64_t*>(p + jobs_at(n)); }  // device
+    uint32_t* list() const { return reinterpret_cast<uint32_t*>(p + cols_bytes(n)); }  // host
+    uint64_t inputs_bytes() const { return 5 * n * 8; }           // base .. W: one H2D
+    uint64_t results_bytes() const { return 4 * n * 8 + 4 * n; }  // need, X, W, the free slot, status: one D2H
+};
+
+// A walk pass over k connections: the list, the count of messages found per connection, and the
+// message table (M entries of packed length, framed length per connection), u32 each. The counts
+// and the table come back as one copy.
+struct RoundBlock {
+    uint8_t* p;
+    uint64_t k, M;
+    static uint64_t tab_words(uint64_t k, uint64_t M) { return 2 * k * M; }
+    static uint64_t device_bytes(uint64_t k, uint64_t M) { return 4 * (2 * k + tab_words(k, M)) + 256; }
+    static uint64_t results_bytes(uint64_t k, uint64_t M) { return 4 * (k + tab_words(k, M)); }
+    uint32_t* list() const { return reinterpret_cast<uint32_t*>(p); }
+    uint32_t* counts() const { return list() + k; }
+    uint32_t* table() const { return counts() + k; }
+};
+// Its results on the host: the counts, then the table.
+struct RoundResults {
+    const uint32_t* p;
+    uint64_t k, M;
+    uint32_t count(uint32_t j) const { return p[j]; }
+    const uint32_t* messages(uint32_t j) const { return p + k + 2 * j * M; }  // packed, framed length per message
+};
+
+// The window tables of a walk pass over k connections with T windows in all: the tables' queue
+// (cpk::framer_spec_bytes; its u64 at u32 index 8 is T), then per listed connection the first
+// window and the count (u32), then its bytes' arena offset and length (u64). A pass without
+// tables has p null, and every part of the block is null with it.
+struct SpecBlock {
+    uint8_t* p;
+    uint64_t k, qb, ab;
+    SpecBlock(uint32_t k_, uint64_t T)
+        : p(nullptr), k(k_), qb((cpk::framer_spec_bytes(k_, T) + 15) & ~15ull), ab((8ull * k_ + 15) & ~15ull) {}
+    uint64_t device_bytes() const { return qb + ab + 16 * k + 64; }
+    template <class T>
+    T* at(uint64_t byte, uint64_t i) const { return p ? reinterpret_cast<T*>(p + byte) + i : nullptr; }
+    uint32_t* queue() const { return at<uint32_t>(0, 0); }
+    uint32_t* windows() const { return at<uint32_t>(0, 8); }
+    uint32_t* first() const { return at<uint32_t>(qb, 0); }
+    uint32_t* count() const { return at<uint32_t>(qb, k); }
+    uint64_t* off() const { return at<uint64_t>(qb + ab, 0); }
+    uint64_t* len() const { return at<uint64_t>(qb + ab, k); }
+};
+
+// Device context for the single-buffer host entry points: device buffers and pinned host
+// staging (the caller's pageable bytes are copied into pinned memory, so the H2D / D2H copies
+// run as DMA at full PCIe rate), one stream, the meta block's host copy in pinned memory too.
 struct HostCtx {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    uint8_t* d_in = nullptr;
-    size_t in_cap = 0;
-    uint8_t* d_out = nullptr;
-    size_t out_cap = 0;
-    uint8_t* h_in = nullptr;  // pinned staging
-    size_t h_in_cap = 0;
-    uint8_t* h_out = nullptr;
-    size_t h_out_cap = 0;
-    uint64_t* d_meta = nullptr;  // in_off, in_len, out_off, out_cap, out_len, status (as u64), consumed
+    Buf<false> d_in, d_out;
+    Buf<true> h_in, h_out;
+    uint64_t* d_meta = nullptr;  // SingleMeta
     uint64_t* h_meta = nullptr;
 
     int init() {
         if (stream) return CAPNP_PACKED_OK;
         hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
         if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
-        e = hipMalloc(&d_meta, 8 * sizeof(uint64_t));
+        e = hipMalloc(&d_meta, SingleMeta::kAllocBytes);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(meta)");
-        e = hipHostMalloc(reinterpret_cast<void**>(&h_meta), 8 * sizeof(uint64_t), hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(meta)");
-        return CAPNP_PACKED_OK;
-    }
-    static size_t grow(size_t need) { return need < 65536 ? 65536 : need + need / 2; }
-    // A buffer grown by an unusually large call is given back on the next call that needs a
-    // quarter of it or less (above 64 MiB): the context does not pin its peak for the process.
-    static bool keep(size_t need, size_t cap) { return need <= cap && !(cap > (64u << 20) && need <= cap / 4); }
-    int reserve(uint8_t** p, size_t* cap, size_t need) {
-        if (*p && keep(need, *cap)) return CAPNP_PACKED_OK;
-        if (need > (SIZE_MAX / 3) * 2) return fail(CAPNP_PACKED_OUT_OF_SPACE, "workspace size overflows size_t");
-        const size_t want = grow(need);
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        hipError_t e = hipMalloc(p, want);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(workspace)");
-        *cap = want;
-        return CAPNP_PACKED_OK;
-    }
-    int reserve_host(uint8_t** p, size_t* cap, size_t need) {
-        if (*p && keep(need, *cap)) return CAPNP_PACKED_OK;
-        if (need > (SIZE_MAX / 3) * 2) return fail(CAPNP_PACKED_OUT_OF_SPACE, "staging size overflows size_t");
-        const size_t want = grow(need);
-        if (*p) (void)hipHostFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(p), want, hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(staging)");
-        *cap = want;
-        return CAPNP_PACKED_OK;
+        e = hipHostMalloc(reinterpret_cast<void**>(&h_meta), SingleMeta::kAllocBytes, hipHostMallocDefault);
+        return launched(e, "hipHostMalloc(meta)");
     }
 };
 
@@ -137,12 +281,7 @@ struct FrameCtx {
     hipStream_t copy = nullptr;   // frames D2H, overlapping the next round
     hipEvent_t ev_done[2] = {nullptr, nullptr};  // round into d_out[b] decoded
     hipEvent_t ev_copied[2] = {nullptr, nullptr};  // frames of d_out[b] on the host
-    uint8_t* d_in = nullptr;
-    size_t in_cap = 0;
-    uint8_t* d_out[2] = {nullptr, nullptr};
-    size_t out_cap[2] = {0, 0};
-    uint8_t* d_meta = nullptr;
-    size_t meta_cap = 0;
+    Buf<false> d_in, d_out[2], d_meta;
 
     int init() {
         if (stream) return CAPNP_PACKED_OK;
@@ -152,19 +291,7 @@ struct FrameCtx {
             e = hipEventCreateWithFlags(&ev_done[b], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_copied[b], hipEventDisableTiming);
         }
-        return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "hipStreamCreate(framer)");
-    }
-    int reserve(uint8_t** p, size_t* cap, size_t need) {
-        if (need <= *cap && *p) return CAPNP_PACKED_OK;
-        if (need > (SIZE_MAX / 3) * 2) return fail(CAPNP_PACKED_OUT_OF_SPACE, "workspace size overflows size_t");
-        const size_t want = need < 65536 ? 65536 : need + need / 2;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), want);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(framer)");
-        *cap = want;
-        return CAPNP_PACKED_OK;
+        return launched(e, "hipStreamCreate(framer)");
     }
 };
 
@@ -173,87 +300,152 @@ FrameCtx g_fr;
 // Largest unpacked size of n packed bytes: a 2-byte zero-run record expands to 256 words.
 uint64_t unpack_bound(size_t n) { return n > (UINT64_MAX / 1024) ? UINT64_MAX : 1024ull * n; }
 
-// Run one unit through a batch kernel. kind: 0 encode, 1 decode, 2 decoded size, 3 encoded size,
-// 4 read message (reader.zig:84-156; *used_out = packed bytes consumed). The input crosses
-// PCIe once (pinned staging), the kernels run with an output slot of `slot` bytes, and the
-// output comes back only when the unit is OK; *len_out is out_len (for OUT_OF_SPACE: the
-// size the unit needs).
+// Run one unit through a batch kernel (kReadMessage: reader.zig:84-156; *used_out = packed bytes
+// consumed). The input crosses PCIe once (pinned staging), the kernels run with an output slot
+// of `slot` bytes, and the output comes back only when the unit is OK; *len_out is out_len (for
+// OUT_OF_SPACE: the size the unit needs).
 // reuse_in: the device already holds `in` from the previous call (a retry with a larger slot).
 // Single units up to these sizes take one kernel (cpk::launch_decode_one / launch_encode_one);
 // DESIGN.md §6.1 has the measured crossover.
 constexpr size_t kFastDecodeMax = 24 * 1024;  // packed bytes (the serial window walk passes the batch path near 32 KB)
 constexpr size_t kFastEncodeMax = 4096;       // unpacked bytes: one 512-word tile
 
-int run_single(int kind, const uint8_t* in, size_t n, uint8_t* out, size_t slot, uint64_t* len_out,
-               uint64_t* used_out = nullptr, bool reuse_in = false, uint32_t dialect = CAPNP_PACKED_DIALECT_ZIG) {
+enum class Single { kEncode, kDecode, kDecodedSize, kEncodedSize, kReadMessage };
+
+int run_single(Single kind, const uint8_t* in, size_t n, uint8_t* out, size_t slot, uint64_t* len_out,
+               uint64_t* used_out, bool reuse_in, uint32_t dialect) {
     int st = g_ctx.init();
     if (st) return st;
     if (n > SIZE_MAX - 16 || slot > SIZE_MAX - 16) return fail(CAPNP_PACKED_OUT_OF_SPACE, "buffer size overflows size_t");
     if (!reuse_in) {
-        if ((st = g_ctx.reserve(&g_ctx.d_in, &g_ctx.in_cap, n + 16))) return st;
-        if ((st = g_ctx.reserve_host(&g_ctx.h_in, &g_ctx.h_in_cap, n + 16))) return st;
+        if ((st = g_ctx.d_in.reserve(n + 16, kSingleDevice))) return st;
+        if ((st = g_ctx.h_in.reserve(n + 16, kSingleStaging))) return st;
     }
-    const bool write = (kind == 0 || kind == 1 || kind == 4);
-    if (write && (st = g_ctx.reserve(&g_ctx.d_out, &g_ctx.out_cap, slot + 16))) return st;
-    uint64_t* const hm = g_ctx.h_meta;
+    const bool encodes = kind == Single::kEncode || kind == Single::kEncodedSize;
+    const bool write = kind == Single::kEncode || kind == Single::kDecode || kind == Single::kReadMessage;
+    if (write && (st = g_ctx.d_out.reserve(slot + 16, kSingleDevice))) return st;
     // one kernel for a single unit the one-unit kernels take (kFastDecodeMax / kFastEncodeMax)
-    const bool one = n > 0 && ((kind == 1 && n <= kFastDecodeMax) || ((kind == 0 || kind == 3) && n <= kFastEncodeMax));
-    uint64_t meta[7] = {0, n, 0, slot, 0, 0, 0};  // in_off, in_len, out_off, out_cap, out_len, status, consumed
-    if (one && kind == 1) {
-        const int32_t need = cpk::decode_one_status();  // decode_wave_kernel<kWvMarked> takes marked units
-        std::memcpy(&meta[5], &need, sizeof(need));
-    }
-    std::memcpy(hm, meta, sizeof(meta));
+    const bool one = n > 0 && ((kind == Single::kDecode && n <= kFastDecodeMax) || (encodes && n <= kFastEncodeMax));
+    const SingleMeta hm(g_ctx.h_meta), m(g_ctx.d_meta);
+    std::memset(hm.p, 0, SingleMeta::kBytes);
+    *hm.in_len() = n;
+    *hm.out_cap() = slot;
+    // decode_wave_kernel<kWvMarked> takes marked units
+    if (one && kind == Single::kDecode) *hm.status() = cpk::decode_one_status();
     hipStream_t s = g_ctx.stream;
     hipError_t e = hipSuccess;
     if (n && !reuse_in) {
-        std::memcpy(g_ctx.h_in, in, n);
-        e = hipMemcpyAsync(g_ctx.d_in, g_ctx.h_in, n, hipMemcpyHostToDevice, s);
+        std::memcpy(g_ctx.h_in.p, in, n);
+        e = hipMemcpyAsync(g_ctx.d_in.p, g_ctx.h_in.p, n, hipMemcpyHostToDevice, s);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(g_ctx.d_meta, hm, sizeof(meta), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m.p, hm.p, SingleMeta::kBytes, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D)");
-    uint64_t* m = g_ctx.d_meta;
-    int32_t* d_status = reinterpret_cast<int32_t*>(m + 5);
-    if (one && kind == 1)
-        e = cpk::launch_decode_one(g_ctx.d_in, m, m + 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, s);
-    else if ((kind == 0 || kind == 3) && dialect == CAPNP_PACKED_DIALECT_CXX)
-        e = cpk::launch_encode_cxx(g_ctx.d_in, m, m + 1, 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, s);
+    const uint8_t* const d_in = g_ctx.d_in.p;
+    uint8_t* const d_out = g_ctx.d_out.p;
+    if (one && kind == Single::kDecode)
+        e = cpk::launch_decode_one(d_in, m.in_off(), m.in_len(), d_out, m.out_off(), m.out_cap(), m.out_len(),
+                                   m.status(), s);
+    else if (encodes && dialect == CAPNP_PACKED_DIALECT_CXX)
+        e = cpk::launch_encode_cxx(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
+                                   m.status(), write, s);
     else if (one)
-        e = cpk::launch_encode_one(g_ctx.d_in, m, m + 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, s);
-    else if (kind == 0 || kind == 3)
-        e = cpk::launch_encode(g_ctx.d_in, m, m + 1, 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, nullptr, 0,
-                               s);
-    else if (kind == 4)
-        e = cpk::launch_read_message(g_ctx.d_in, m, m + 1, 1, g_ctx.d_out, m + 2, m + 3, m + 4, m + 6, d_status, s);
+        e = cpk::launch_encode_one(d_in, m.in_off(), m.in_len(), d_out, m.out_off(), m.out_cap(), m.out_len(),
+                                   m.status(), write, s);
+    else if (encodes)
+        e = cpk::launch_encode(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
+                               m.status(), write, nullptr, 0, s);
+    else if (kind == Single::kReadMessage)
+        e = cpk::launch_read_message(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
+                                     m.consumed(), m.status(), s);
     else
-        e = cpk::launch_decode(g_ctx.d_in, m, m + 1, 1, g_ctx.d_out, m + 2, m + 3, m + 4, d_status, write, nullptr, 0,
-                               s);
+        e = cpk::launch_decode(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
+                               m.status(), write, nullptr, 0, s);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    e = hipMemcpyAsync(hm, g_ctx.d_meta, sizeof(meta), hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(hm.p, m.p, SingleMeta::kBytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H)");
-    int32_t status;
-    std::memcpy(&status, &hm[5], sizeof(status));
-    *len_out = hm[4];
-    if (used_out) *used_out = hm[6];
-    if (status == CAPNP_PACKED_OK && write && hm[4]) {
-        const size_t len = (size_t)hm[4];
-        if ((st = g_ctx.reserve_host(&g_ctx.h_out, &g_ctx.h_out_cap, len))) return st;
-        e = hipMemcpyAsync(g_ctx.h_out, g_ctx.d_out, len, hipMemcpyDeviceToHost, s);
+    const int32_t status = *hm.status();
+    const uint64_t out_len = *hm.out_len();
+    *len_out = out_len;
+    if (used_out) *used_out = *hm.consumed();
+    if (status == CAPNP_PACKED_OK && write && out_len) {
+        const size_t len = (size_t)out_len;
+        if ((st = g_ctx.h_out.reserve(len, kSingleStaging))) return st;
+        e = hipMemcpyAsync(g_ctx.h_out.p, d_out, len, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy(D2H out)");
-        std::memcpy(out, g_ctx.h_out, len);
+        std::memcpy(out, g_ctx.h_out.p, len);
     }
     if (status != CAPNP_PACKED_OK) g_last_error = capnp_packed_status_name(status);
     return status;
 }
 
-int check_batch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
-                const uint64_t* d_len, const int32_t* d_status) {
+// capnp_packed_encode / _dialect with the dialect known to be one of the two
+int encode_single(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, uint32_t dialect) {
+    if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
+    *out_len = 0;
+    if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
+    if (n % 8) return fail(CAPNP_PACKED_INVALID_MESSAGE_SIZE, "InvalidMessageSize");  // message.zig:201
+    int st = ensure_device();
+    if (st) return st;
+    std::lock_guard<std::mutex> lock(g_ctx.mu);
+    size_t bound = capnp_packed_encode_bound(n);
+    uint64_t len = 0;
+    st = run_single(Single::kEncode, in, n, out, cap < bound ? cap : bound, &len, nullptr, false, dialect);
+    *out_len = (size_t)len;
+    return st;
+}
+
+int check_batch(const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n, const uint64_t* d_len,
+                const int32_t* d_status) {
     if (n == 0) return CAPNP_PACKED_OK;
     if (!d_in_off || !d_in_len || !d_len || !d_status) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-    (void)d_in;
     return ensure_device();
+}
+
+// The kernels address the workspace as u32 counters, 16-B table entries and 64-B
+// record stores at 256-B offsets: it must be 256-B aligned (hipMalloc's alignment).
+int check_ws(const void* ws, size_t bytes, size_t required, const char* too_small) {
+    if (!ws) return CAPNP_PACKED_OK;
+    if (reinterpret_cast<uintptr_t>(ws) & 255)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "workspace not 256-B aligned");
+    if (bytes < required) return fail(CAPNP_PACKED_INVALID_ARGUMENT, too_small);
+    return CAPNP_PACKED_OK;
+}
+int check_queue_ws(const void* ws, size_t bytes, uint32_t n) {
+    return check_ws(ws, bytes, cpk::queue_bytes(n), "workspace smaller than capnp_packed_batch_workspace_bytes(n)");
+}
+
+// A batch through cpk::launch_encode or launch_decode with an optional caller workspace
+// (write = false: sizes only, no output arrays).
+int codec_batch(decltype(&cpk::launch_encode) launch, const char* what, const uint8_t* d_in, const uint64_t* d_in_off,
+                const uint64_t* d_in_len, uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status, bool write, void* d_workspace,
+                size_t workspace_bytes, void* stream) {
+    int st = check_batch(d_in_off, d_in_len, n, d_out_len, d_status);
+    if (st || n == 0) return st;
+    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
+    if ((st = check_queue_ws(d_workspace, workspace_bytes, n))) return st;
+    return launched(launch(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, write,
+                           d_workspace, workspace_bytes, static_cast<hipStream_t>(stream)),
+                    what);
+}
+
+// capnp_packed_encode_message_batch / _dialect with the dialect known to be one of the two
+int encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len, const uint32_t* d_seg_first,
+                         const uint32_t* d_seg_count, uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                         const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status, bool cxx, void* stream) {
+    if (n == 0) return CAPNP_PACKED_OK;
+    if (!d_seg_first || !d_seg_count || !d_out_len || !d_status)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    const bool write = d_out != nullptr;
+    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
+    int st = ensure_device();
+    if (st) return st;
+    const auto launch = cxx ? cpk::launch_encode_message_cxx : cpk::launch_encode_message;
+    return launched(launch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off, d_out_cap, d_out_len,
+                           d_status, write, static_cast<hipStream_t>(stream)),
+                    "encode-message launch");
 }
 
 }  // namespace
@@ -296,36 +488,14 @@ const char* capnp_packed_status_name(int status) {
 size_t capnp_packed_encode_bound(size_t n) { return 10 * (n / 8); }
 
 int capnp_packed_encode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len) {
-    if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
-    *out_len = 0;
-    if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
-    if (n % 8) return fail(CAPNP_PACKED_INVALID_MESSAGE_SIZE, "InvalidMessageSize");  // message.zig:201
-    int st = ensure_device();
-    if (st) return st;
-    std::lock_guard<std::mutex> lock(g_ctx.mu);
-    size_t bound = capnp_packed_encode_bound(n);
-    uint64_t len = 0;
-    st = run_single(0, in, n, out, cap < bound ? cap : bound, &len);
-    *out_len = (size_t)len;
-    return st;
+    return encode_single(in, n, out, cap, out_len, CAPNP_PACKED_DIALECT_ZIG);
 }
 
 int capnp_packed_encode_dialect(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
                                 uint32_t dialect) {
-    if (dialect == CAPNP_PACKED_DIALECT_ZIG) return capnp_packed_encode(in, n, out, cap, out_len);
-    if (dialect != CAPNP_PACKED_DIALECT_CXX) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
-    if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
-    *out_len = 0;
-    if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
-    if (n % 8) return fail(CAPNP_PACKED_INVALID_MESSAGE_SIZE, "InvalidMessageSize");
-    int st = ensure_device();
-    if (st) return st;
-    std::lock_guard<std::mutex> lock(g_ctx.mu);
-    size_t bound = capnp_packed_encode_bound(n);
-    uint64_t len = 0;
-    st = run_single(0, in, n, out, cap < bound ? cap : bound, &len, nullptr, false, dialect);
-    *out_len = (size_t)len;
-    return st;
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    return encode_single(in, n, out, cap, out_len, dialect);
 }
 
 int capnp_packed_decoded_size(const uint8_t* in, size_t n, size_t* out_size) {
@@ -336,7 +506,7 @@ int capnp_packed_decoded_size(const uint8_t* in, size_t n, size_t* out_size) {
     if (st) return st;
     std::lock_guard<std::mutex> lock(g_ctx.mu);
     uint64_t len = 0;
-    st = run_single(2, in, n, nullptr, 0, &len);
+    st = run_single(Single::kDecodedSize, in, n, nullptr, 0, &len, nullptr, false, CAPNP_PACKED_DIALECT_ZIG);
     if (st == CAPNP_PACKED_OK) *out_size = (size_t)len;
     return st;
 }
@@ -359,9 +529,9 @@ int capnp_packed_decode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, s
     const uint64_t guess = n > (UINT64_MAX / 8) ? UINT64_MAX : (8ull * n < 65536 ? 65536 : 8ull * n);
     const uint64_t first = room < guess ? room : guess;
     uint64_t len = 0;
-    st = run_single(1, in, n, out, (size_t)first, &len);
+    st = run_single(Single::kDecode, in, n, out, (size_t)first, &len, nullptr, false, CAPNP_PACKED_DIALECT_ZIG);
     if (st == CAPNP_PACKED_OUT_OF_SPACE && first < room && len <= room)
-        st = run_single(1, in, n, out, (size_t)len, &len, nullptr, true);
+        st = run_single(Single::kDecode, in, n, out, (size_t)len, &len, nullptr, true, CAPNP_PACKED_DIALECT_ZIG);
     *out_len = (st == CAPNP_PACKED_OK || st == CAPNP_PACKED_OUT_OF_SPACE) ? (size_t)len : 0;
     return st;
 }
@@ -386,8 +556,7 @@ uint32_t capnp_packed_set_launch_flags(uint32_t flags) {
 int capnp_packed_stream_release(void* stream) {
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::release_stream(static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "stream release");
+    return launched(cpk::release_stream(static_cast<hipStream_t>(stream)), "stream release");
 }
 
 int capnp_packed_stream_queue_info(void* stream, size_t* bytes, uint32_t* kept) {
@@ -409,28 +578,12 @@ int capnp_packed_stream_contexts(uint32_t* count) {
     return CAPNP_PACKED_OK;
 }
 
-// The kernels address the workspace as u32 counters, 16-B table entries and 64-B
-// record stores at 256-B offsets: it must be 256-B aligned (hipMalloc's alignment).
-static int check_ws(const void* ws, size_t bytes, uint32_t n) {
-    if (!ws) return CAPNP_PACKED_OK;
-    if (reinterpret_cast<uintptr_t>(ws) & 255)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "workspace not 256-B aligned");
-    if (bytes < cpk::queue_bytes(n))
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "workspace smaller than capnp_packed_batch_workspace_bytes(n)");
-    return CAPNP_PACKED_OK;
-}
-
 int capnp_packed_encode_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                  uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                  uint64_t* d_out_len, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
                                  void* stream) {
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
-    if (st || n == 0) return st;
-    if (!d_out_off || !d_out_cap) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
-    if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;
-    hipError_t e = cpk::launch_encode(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
-                                      d_status, true, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode launch");
+    return codec_batch(cpk::launch_encode, "encode launch", d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap,
+                       d_out_len, d_status, true, d_workspace, workspace_bytes, stream);
 }
 
 int capnp_packed_encode_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -451,21 +604,17 @@ int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_
             return capnp_packed_encode_batch_ws(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
                                                 d_status, d_workspace, workspace_bytes, stream);
         // sizes only: capnp_packed_encoded_size_batch with the caller's workspace
-        int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
-        if (st || n == 0) return st;
-        if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;
-        hipError_t e = cpk::launch_encode(d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr, d_out_len, d_status,
-                                          false, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-        return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-size launch");
+        return codec_batch(cpk::launch_encode, "encode-size launch", d_in, d_in_off, d_in_len, n, nullptr, nullptr,
+                           nullptr, d_out_len, d_status, false, d_workspace, workspace_bytes, stream);
     }
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
+    int st = check_batch(d_in_off, d_in_len, n, d_out_len, d_status);
     if (st || n == 0) return st;
     const bool write = d_out != nullptr;
     if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
-    if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;  // checked, not used: one kernel
-    hipError_t e = cpk::launch_encode_cxx(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
-                                          d_status, write, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode launch");
+    if ((st = check_queue_ws(d_workspace, workspace_bytes, n))) return st;  // checked, not used: one kernel
+    return launched(cpk::launch_encode_cxx(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
+                                           d_status, write, static_cast<hipStream_t>(stream)),
+                    "encode launch");
 }
 
 size_t capnp_packed_encode_dense_workspace_bytes(uint32_t n) { return cpk::dense_workspace_bytes(n); }
@@ -482,40 +631,30 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
         if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
             return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
         if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
-        if (reinterpret_cast<uintptr_t>(d_workspace) & 255)
-            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "workspace not 256-B aligned");
-        if (workspace_bytes < cpk::dense_workspace_bytes(n))
-            return fail(CAPNP_PACKED_INVALID_ARGUMENT,
-                        "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
+        int st = check_ws(d_workspace, workspace_bytes, cpk::dense_workspace_bytes(n),
+                          "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
+        if (st) return st;
     }
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
-                                            d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, d_workspace,
-                                            static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "dense encode launch");
+    return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
+                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, d_workspace,
+                                             static_cast<hipStream_t>(stream)),
+                    "dense encode launch");
 }
 
 int capnp_packed_encoded_size_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint64_t* d_out_len, int32_t* d_status, void* stream) {
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
-    if (st || n == 0) return st;
-    hipError_t e = cpk::launch_encode(d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr, d_out_len, d_status,
-                                      false, nullptr, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-size launch");
+    return codec_batch(cpk::launch_encode, "encode-size launch", d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr,
+                       d_out_len, d_status, false, nullptr, 0, stream);
 }
 
 int capnp_packed_decode_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                  uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                  uint64_t* d_out_len, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
                                  void* stream) {
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
-    if (st || n == 0) return st;
-    if (!d_out_off || !d_out_cap) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
-    if ((st = check_ws(d_workspace, workspace_bytes, n))) return st;
-    hipError_t e = cpk::launch_decode(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
-                                      d_status, true, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "decode launch");
+    return codec_batch(cpk::launch_decode, "decode launch", d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap,
+                       d_out_len, d_status, true, d_workspace, workspace_bytes, stream);
 }
 
 int capnp_packed_decode_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -527,23 +666,20 @@ int capnp_packed_decode_batch(const uint8_t* d_in, const uint64_t* d_in_off, con
 
 int capnp_packed_decoded_size_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint64_t* d_out_len, int32_t* d_status, void* stream) {
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
-    if (st || n == 0) return st;
-    hipError_t e = cpk::launch_decode(d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr, d_out_len, d_status,
-                                      false, nullptr, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "decode-size launch");
+    return codec_batch(cpk::launch_decode, "decode-size launch", d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr,
+                       d_out_len, d_status, false, nullptr, 0, stream);
 }
 
 int capnp_packed_read_message_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
                                     const uint64_t* d_out_cap, uint64_t* d_out_len, uint64_t* d_consumed,
                                     int32_t* d_status, void* stream) {
-    int st = check_batch(d_in, d_in_off, d_in_len, n, d_out_len, d_status);
+    int st = check_batch(d_in_off, d_in_len, n, d_out_len, d_status);
     if (st || n == 0) return st;
     if (!d_out_off || !d_out_cap || !d_consumed) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output arrays");
-    hipError_t e = cpk::launch_read_message(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
-                                            d_consumed, d_status, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "read-message launch");
+    return launched(cpk::launch_read_message(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
+                                             d_consumed, d_status, static_cast<hipStream_t>(stream)),
+                    "read-message launch");
 }
 
 int capnp_packed_read_message(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
@@ -560,7 +696,8 @@ int capnp_packed_read_message(const uint8_t* in, size_t n, uint8_t* out, size_t 
     // device slot is sized by what the reader can write, not by the caller's buffer
     const size_t kMaxFramed = (257ull + 8ull * 1024 * 1024) * 8;
     uint64_t len = 0, used = 0;
-    st = run_single(4, in, n, out, cap < kMaxFramed ? cap : kMaxFramed, &len, &used);
+    st = run_single(Single::kReadMessage, in, n, out, cap < kMaxFramed ? cap : kMaxFramed, &len, &used, false,
+                    CAPNP_PACKED_DIALECT_ZIG);
     *out_len = (size_t)len;
     *consumed = (size_t)used;
     return st;
@@ -570,16 +707,8 @@ int capnp_packed_encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t*
                                       const uint32_t* d_seg_first, const uint32_t* d_seg_count, uint32_t n,
                                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                       uint64_t* d_out_len, int32_t* d_status, void* stream) {
-    if (n == 0) return CAPNP_PACKED_OK;
-    if (!d_seg_first || !d_seg_count || !d_out_len || !d_status)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-    const bool write = d_out != nullptr;
-    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
-    int st = ensure_device();
-    if (st) return st;
-    hipError_t e = cpk::launch_encode_message(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
-                                              d_out_cap, d_out_len, d_status, write, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-message launch");
+    return encode_message_batch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off, d_out_cap,
+                                d_out_len, d_status, false, stream);
 }
 
 int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len,
@@ -587,21 +716,10 @@ int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const u
                                               uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                               uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
                                               void* stream) {
-    if (dialect == CAPNP_PACKED_DIALECT_ZIG)
-        return capnp_packed_encode_message_batch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
-                                                 d_out_cap, d_out_len, d_status, stream);
-    if (dialect != CAPNP_PACKED_DIALECT_CXX) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
-    if (n == 0) return CAPNP_PACKED_OK;
-    if (!d_seg_first || !d_seg_count || !d_out_len || !d_status)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-    const bool write = d_out != nullptr;
-    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
-    int st = ensure_device();
-    if (st) return st;
-    hipError_t e = cpk::launch_encode_message_cxx(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off,
-                                                  d_out_cap, d_out_len, d_status, write,
-                                                  static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "encode-message launch");
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    return encode_message_batch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off, d_out_cap,
+                                d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, stream);
 }
 
 int capnp_packed_message_init_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -612,9 +730,9 @@ int capnp_packed_message_init_batch(const uint8_t* d_in, const uint64_t* d_in_of
         return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::launch_message_init(d_in, d_in_off, d_in_len, n, max_segs, d_seg_count, d_seg_off, d_seg_len,
-                                            d_status, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "message-init launch");
+    return launched(cpk::launch_message_init(d_in, d_in_off, d_in_len, n, max_segs, d_seg_count, d_seg_off, d_seg_len,
+                                             d_status, static_cast<hipStream_t>(stream)),
+                    "message-init launch");
 }
 
 int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -624,9 +742,9 @@ int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
     if (!d_in_off || !d_in_len || !d_status) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::launch_validate(d_in, d_in_off, d_in_len, n, segment_count_limit, traversal_limit_words,
-                                        nesting_limit, d_status, d_words, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "validate launch");
+    return launched(cpk::launch_validate(d_in, d_in_off, d_in_len, n, segment_count_limit, traversal_limit_words,
+                                         nesting_limit, d_status, d_words, static_cast<hipStream_t>(stream)),
+                    "validate launch");
 }
 
 size_t capnp_packed_scan_scratch_bytes(uint32_t n) { return cpk::scan_scratch_bytes(n); }
@@ -637,9 +755,9 @@ int capnp_packed_lengths_to_offsets(const uint64_t* d_len, uint32_t n, uint64_t 
     if (scratch_bytes < cpk::scan_scratch_bytes(n)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "scratch too small");
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::launch_scan(d_len, n, base, d_off, static_cast<uint64_t*>(d_scratch),
-                                    static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "scan launch");
+    return launched(cpk::launch_scan(d_len, n, base, d_off, static_cast<uint64_t*>(d_scratch),
+                                     static_cast<hipStream_t>(stream)),
+                    "scan launch");
 }
 
 int capnp_packed_generate(uint8_t* d_out, uint64_t n_units, uint64_t unit_bytes, uint64_t unit_base,
@@ -648,9 +766,9 @@ int capnp_packed_generate(uint8_t* d_out, uint64_t n_units, uint64_t unit_bytes,
     if (unit_bytes % 8) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unit_bytes % 8 != 0");
     int st = ensure_device();
     if (st) return st;
-    hipError_t e = cpk::launch_generate(d_out, n_units, unit_bytes, unit_base, seed, zero_thresh,
-                                        static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "generate launch");
+    return launched(cpk::launch_generate(d_out, n_units, unit_bytes, unit_base, seed, zero_thresh,
+                                         static_cast<hipStream_t>(stream)),
+                    "generate launch");
 }
 
 int capnp_packed_frame_connections(const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
@@ -676,12 +794,12 @@ int capnp_packed_frame_connections(const uint8_t* in, uint64_t in_bytes, const u
     struct CopiesDone {
         ~CopiesDone() { (void)hipStreamSynchronize(g_fr.copy); }
     } copies_done;
-    if ((st = g_fr.reserve(&g_fr.d_in, &g_fr.in_cap, in_bytes + 16))) return st;
-    if ((st = g_fr.reserve(&g_fr.d_meta, &g_fr.meta_cap, (size_t)n * 7 * sizeof(uint64_t)))) return st;
+    if ((st = g_fr.d_in.reserve(in_bytes + 16, kFrameRounds))) return st;
+    if ((st = g_fr.d_meta.reserve(RoundMeta::bytes(n), kFrameRounds))) return st;
     const hipStream_t s = g_fr.stream;
-    hipError_t e = in_bytes ? hipMemcpyAsync(g_fr.d_in, in, in_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    hipError_t e = in_bytes ? hipMemcpyAsync(g_fr.d_in.p, in, in_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D input)");
-    std::vector<uint64_t> used(n, 0), cap(n), meta(7ull * n);  // meta: in_off, in_len, out_off, out_cap | len, cons, st
+    std::vector<uint64_t> used(n, 0), cap(n), meta(RoundMeta::bytes(n) / 8);
     std::vector<uint32_t> idx(n);
     std::vector<uint8_t> live(n);
     for (uint32_t c = 0; c < n; ++c) {
@@ -698,44 +816,35 @@ int capnp_packed_frame_connections(const uint8_t* in, uint64_t in_bytes, const u
         for (uint32_t c = 0; c < n; ++c)
             if (live[c] && used[c] < in_len[c]) idx[k++] = c;
         if (k == 0) break;
-        uint64_t* const h_in_off = meta.data();
-        uint64_t* const h_in_len = h_in_off + k;
-        uint64_t* const h_out_off = h_in_off + 2 * k;
-        uint64_t* const h_out_cap = h_in_off + 3 * k;
+        const RoundMeta h{{meta.data(), k}}, d{{reinterpret_cast<uint64_t*>(g_fr.d_meta.p), k}};
         uint64_t slots = 0;
         for (uint32_t j = 0; j < k; ++j) {
             const uint32_t c = idx[j];
-            h_in_off[j] = in_off[c] + used[c];
-            h_in_len[j] = in_len[c] - used[c];
-            h_out_cap[j] = (cap[c] + 7) & ~7ull;
-            h_out_off[j] = slots;
-            slots += h_out_cap[j];
+            h.in_off()[j] = in_off[c] + used[c];
+            h.in_len()[j] = in_len[c] - used[c];
+            h.out_cap()[j] = (cap[c] + 7) & ~7ull;
+            h.out_off()[j] = slots;
+            slots += h.out_cap()[j];
         }
         // round r - 2's frames left d_out[b] before it is reused (or reallocated)
         e = hipEventSynchronize(g_fr.ev_copied[b]);
         if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize(frames copy)");
-        if ((st = g_fr.reserve(&g_fr.d_out[b], &g_fr.out_cap[b], slots + 16))) return st;
-        uint64_t* const dm = reinterpret_cast<uint64_t*>(g_fr.d_meta);
-        e = hipMemcpyAsync(dm, h_in_off, 4ull * k * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+        if ((st = g_fr.d_out[b].reserve(slots + 16, kFrameRounds))) return st;
+        e = hipMemcpyAsync(d.p, h.p, h.inputs_bytes(), hipMemcpyHostToDevice, s);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D round)");
-        int32_t* const d_st = reinterpret_cast<int32_t*>(dm + 6ull * k);
-        e = cpk::launch_read_message(g_fr.d_in, dm, dm + k, k, g_fr.d_out[b], dm + 2ull * k, dm + 3ull * k,
-                                     dm + 4ull * k, dm + 5ull * k, d_st, s);
+        e = cpk::launch_read_message(g_fr.d_in.p, d.in_off(), d.in_len(), k, g_fr.d_out[b].p, d.out_off(), d.out_cap(),
+                                     d.out_len(), d.consumed(), d.status(), s);
         if (e == hipSuccess) e = hipEventRecord(g_fr.ev_done[b], s);
         if (e != hipSuccess) return hip_fail(e, "read-message launch");
-        uint64_t* const h_len = h_in_off + 4 * k;
-        uint64_t* const h_cons = h_in_off + 5 * k;
-        int32_t* const h_st = reinterpret_cast<int32_t*>(h_in_off + 6 * k);
-        e = hipMemcpyAsync(h_len, dm + 4ull * k, 2ull * k * sizeof(uint64_t) + k * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(h.out_len(), d.out_len(), h.results_bytes(), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H round)");
         // the round's frames go to `frames` as one copy of its slots up to the last good one
         uint64_t span = 0;
         uint32_t good = 0;
         for (uint32_t j = 0; j < k; ++j)
-            if (h_st[j] == CAPNP_PACKED_OK) {
-                span = h_out_off[j] + h_len[j];
+            if (h.status()[j] == CAPNP_PACKED_OK) {
+                span = h.out_off()[j] + h.out_len()[j];
                 ++good;
             }
         if (good) {
@@ -743,23 +852,25 @@ int capnp_packed_frame_connections(const uint8_t* in, uint64_t in_bytes, const u
                 return fail(CAPNP_PACKED_OUT_OF_SPACE, "frames buffer or frame table too small");
             // on the copy stream, while the next round decodes into the other buffer
             e = hipStreamWaitEvent(g_fr.copy, g_fr.ev_done[b], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(frames + fcur, g_fr.d_out[b], span, hipMemcpyDeviceToHost, g_fr.copy);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(frames + fcur, g_fr.d_out[b].p, span, hipMemcpyDeviceToHost, g_fr.copy);
             if (e == hipSuccess) e = hipEventRecord(g_fr.ev_copied[b], g_fr.copy);
             if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H frames)");
         }
         for (uint32_t j = 0; j < k; ++j) {
             const uint32_t c = idx[j];
-            const int32_t rs = h_st[j];
+            const int32_t rs = h.status()[j];
+            const uint64_t len = h.out_len()[j];
             if (rs == CAPNP_PACKED_OK) {
-                frame_off[nf] = fcur + h_out_off[j];
-                frame_len[nf] = h_len[j];
+                frame_off[nf] = fcur + h.out_off()[j];
+                frame_len[nf] = len;
                 frame_conn[nf] = c;
                 ++nf;
-                used[c] += h_cons[j];
-                cap[c] = h_len[j] < 8 ? 8 : h_len[j];
+                used[c] += h.consumed()[j];
+                cap[c] = len < 8 ? 8 : len;
             } else if (rs == CAPNP_PACKED_OUT_OF_SPACE) {
                 // the reader reported the framed length: next round, a slot that holds it
-                cap[c] = std::max(2 * cap[c], (uint64_t)h_len[j]);
+                cap[c] = std::max(2 * cap[c], len);
             } else {
                 live[c] = 0;  // END_OF_STREAM: the rest waits for the next read; else the error
                 status[c] = rs;
@@ -783,68 +894,62 @@ int capnp_packed_frame_connections(const uint8_t* in, uint64_t in_bytes, const u
 // (src/rpc/level2/connection.zig:153-203) with Framer state kept across reads
 // (src/rpc/level0/framing.zig:42-90 keeps expected_total; reader.zig:84-156 is one pass).
 // Each connection's unconsumed packed bytes live in a region of one device arena, so a read
-// uploads only its new bytes. Per connection the session keeps the current message's framed
-// length (need, from read_header_kernel once its header is decoded) and where its walk
-// stopped (X: packed bytes from the message start, W: words decoded), so the next read's
-// walk (frame_walk_kernel) starts there: a message split over k reads is uploaded once and
-// walked once. A complete message is decoded straight from the arena into its frame slot
-// (the batch decoder) and copied to the caller's frames buffer.
-//
-// Regions: a connection's region is [off, off + cap) of the arena, its bytes [m0, len) of
-// it. A read that does not fit moves the connection's bytes to a fresh region of twice their
-// size at the arena top (the bytes of a partial message move once per doubling); when the
-// top reaches the end, every connection's bytes move to a new arena of twice the live size.
+// uploads only its new bytes (framer_layout.h has the regions). Per connection the session
+// keeps the current message's framed length (need, from read_header_kernel once its header is
+// decoded) and where its walk stopped (X: packed bytes from the message start, W: words
+// decoded), so the next read's walk (frame_walk_kernel) starts there: a message split over k
+// reads is uploaded once and walked once. A complete message is decoded straight from the
+// arena into its frame slot (the batch decoder) and copied to the caller's frames buffer.
 // ---------------------------------------------------------------------------
+namespace {
+
+// One capnp_packed_framer_read / _readv call: where its frames go, how far it has come, and
+// the pass in hand.
+struct FramerCall {
+    uint8_t* frames;
+    uint64_t frames_cap;
+    uint64_t* frame_off;
+    uint64_t* frame_len;
+    uint32_t* frame_conn;
+    uint32_t max_frames;
+    int32_t* status;
+    uint64_t fcur = 0;  // bytes of `frames` used
+    uint32_t nf = 0;    // frames handed out
+    bool full = false;  // the frames buffer or table ran out
+    std::vector<uint8_t> dead, more;  // dead: an error this call (the connection was reset)
+    std::vector<uint32_t> list;       // the pass's connections
+    std::vector<uint64_t> adv;        // packed bytes of the pass's accepted messages, per connection
+    std::vector<int32_t> perr;        // an error to report once the pass's frames are out
+    std::vector<uint64_t> um;         // the pass's accepted messages: in_off, in_len, out_off, out_cap
+    std::vector<uint32_t> uconn;      // and their connections
+    uint64_t slots = 0;               // bytes of their frame slots
+};
+
+}  // namespace
+
 struct capnp_packed_framer {
     std::mutex mu;
     uint32_t n = 0;
     hipStream_t s = nullptr;
-    uint8_t* arena = nullptr;
-    uint64_t acap = 0, top = 0;
-    std::vector<uint64_t> off, cap, m0, len, need, X, W;  // per connection (host authoritative)
-    // device scratch: per-connection arrays (base, avail, need, X, W, consumed, status),
-    // lists and unit metadata of a round, copy jobs, the input staging and the frame slots
-    uint8_t* d_state = nullptr;
-    uint64_t state_cap = 0;
-    uint8_t* d_stage = nullptr;
-    uint64_t stage_cap = 0;
-    uint8_t* d_frames = nullptr;
-    uint64_t frames_dcap = 0;
-    uint8_t* d_spec = nullptr;  // the walk's window tables (cpk::launch_frame_walk)
-    uint64_t spec_cap = 0;
-    uint8_t* d_round = nullptr;  // a walk pass's list, counts and message table
-    uint64_t round_cap = 0;
-    uint8_t* d_units = nullptr;  // a decode pass's unit metadata (6 u64 per message)
-    uint64_t units_cap = 0;
-    uint8_t* h_stage = nullptr;  // page-locked gather of capnp_packed_framer_readv's reads
-    uint64_t h_stage_cap = 0;
-    // page-locked host sides of a read's metadata copies: per-connection state, a walk pass's
-    // counts and message table, a decode pass's unit metadata (no pageable staging per copy)
-    struct Pinned {
-        uint8_t* p = nullptr;
-        uint64_t cap = 0;
-        int reserve(uint64_t bytes) {
-            if (p && bytes <= cap) return CAPNP_PACKED_OK;
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 4096);
-            const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                p = nullptr;
-                return hip_fail(e, "hipHostMalloc(framer metadata)");
-            }
-            cap = want;
-            return CAPNP_PACKED_OK;
-        }
-        ~Pinned() {
-            if (p) (void)hipHostFree(p);
-        }
-    } pin_state, pin_tab, pin_units, pin_jobs;
-    uint64_t uploaded = 0, moved = 0;  // bytes copied H2D (new reads) and moved between regions
-    uint64_t walk_passes = 0, table_windows = 0;  // walk passes run, windows they built tables for
-    int dev = -1;                      // the device the session was created on
+    int dev = -1;  // the device the session was created on
+    Buf<false> arena;
+    framer_layout::Layout lay;         // per connection (host authoritative): its region and bytes
+    std::vector<uint64_t> need, X, W;  // and the state of its current message
+    Buf<false> d_state;   // StateBlock
+    Buf<false> d_stage;   // a read's new bytes
+    Buf<false> d_frames;  // a decode pass's frame slots
+    Buf<false> d_spec;    // SpecBlock
+    Buf<false> d_round;   // RoundBlock
+    Buf<false> d_units;   // UnitBlock
+    Buf<true> h_stage;    // page-locked gather of capnp_packed_framer_readv's reads
+    // page-locked host sides of a read's metadata copies (no pageable staging per copy)
+    Buf<true> pin_state, pin_tab, pin_units, pin_jobs;
+    uint64_t uploaded = 0;                         // bytes copied H2D (new reads)
+    uint64_t walk_passes = 0, table_windows = 0;   // walk passes run, windows they built tables for
     static constexpr uint32_t kWalkMessages = 64;  // messages a walk pass finds per connection
+    // A read's upload and region copies need no synchronisation of their own: the walk pass's
+    // synchronisation covers them. Until then d_stage and pin_jobs are theirs.
+    bool jobs_inflight = false;
 
     ~capnp_packed_framer() {
         // the session's device is current for the teardown, whatever device the caller has
@@ -858,206 +963,271 @@ struct capnp_packed_framer {
             // class queue), or every session ever created would keep one
             (void)cpk::release_stream(s, dev);
         }
-        if (arena) (void)hipFree(arena);
-        if (d_state) (void)hipFree(d_state);
-        if (d_stage) (void)hipFree(d_stage);
-        if (d_frames) (void)hipFree(d_frames);
-        if (d_spec) (void)hipFree(d_spec);
-        if (d_round) (void)hipFree(d_round);
-        if (d_units) (void)hipFree(d_units);
-        if (h_stage) (void)hipHostFree(h_stage);
+        for (Buf<false>* b : {&arena, &d_state, &d_stage, &d_frames, &d_spec, &d_round, &d_units}) b->release();
+        for (Buf<true>* b : {&h_stage, &pin_state, &pin_tab, &pin_units, &pin_jobs}) b->release();
         if (s) (void)hipStreamDestroy(s);
         if (switched) (void)hipSetDevice(cur);
     }
-    static int grow(uint8_t** p, uint64_t* c, uint64_t need) {
-        if (*p && need <= *c) return CAPNP_PACKED_OK;
-        const uint64_t want = need < 65536 ? 65536 : need + need / 2;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        *c = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), want);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(framer session)");
-        *c = want;
-        return CAPNP_PACKED_OK;
-    }
-    // The copy jobs of a read (host vector hjobs, kept until the stream has consumed it, so a
-    // read's upload and region copies need no synchronisation of their own: the walk pass's
-    // synchronisation covers them).
-    std::vector<uint64_t> hjobs;
-    bool jobs_inflight = false;
-    int settle() {  // the previous read's job upload is done with hjobs
+
+    int settle() {  // the previous read's copies are done with d_stage and pin_jobs
         if (!jobs_inflight) return CAPNP_PACKED_OK;
         jobs_inflight = false;
-        const hipError_t e = hipStreamSynchronize(s);
-        return e == hipSuccess ? CAPNP_PACKED_OK : hip_fail(e, "framer copy jobs");
+        return launched(hipStreamSynchronize(s), "framer copy jobs");
     }
-    // The first `first` jobs run as a launch of their own, before the others (stream order).
-    int run_jobs(std::vector<uint64_t>& jobs, bool wait = true, uint32_t first = 0) {
-        if (jobs.empty()) return CAPNP_PACKED_OK;
-        const uint32_t nj = (uint32_t)(jobs.size() / 3);
-        // the jobs go after the per-connection arrays in the state scratch
-        const uint64_t at = (uint64_t)n * 56 + 256;
-        int st = grow(&d_state, &state_cap, at + jobs.size() * 8 + 64 * (uint64_t)n + 4096);
+
+    // Run a plan's jobs into the arena `to`: as device jobs (dst, src, len) past the state
+    // block's columns. The first `first` jobs run as a launch of their own, before the others
+    // (stream order).
+    int run_jobs(const framer_layout::Job* jobs, uint32_t nj, uint32_t first, uint8_t* to, bool wait) {
+        if (nj == 0) return CAPNP_PACKED_OK;
+        const uint64_t bytes = 3ull * nj * 8;
+        int st = d_state.reserve(StateBlock::device_bytes(n, bytes), kSession);
         if (st) return st;
-        uint64_t* const dj = reinterpret_cast<uint64_t*>(d_state + at);
-        if ((st = pin_jobs.reserve(jobs.size() * 8))) return st;  // page-locked: no staged copy
-        std::memcpy(pin_jobs.p, jobs.data(), jobs.size() * 8);
-        hipError_t e = hipMemcpyAsync(dj, pin_jobs.p, jobs.size() * 8, hipMemcpyHostToDevice, s);
+        uint64_t* const dj = StateBlock{d_state.p, n}.jobs();
+        if ((st = pin_jobs.reserve(bytes, kSessionMeta))) return st;  // page-locked: no staged copy
+        uint64_t* hj = reinterpret_cast<uint64_t*>(pin_jobs.p);
+        for (uint32_t j = 0; j < nj; ++j, hj += 3) {
+            const uint8_t* const from = jobs[j].src_kind == framer_layout::Src::kArena ? arena.p : d_stage.p;
+            hj[0] = reinterpret_cast<uint64_t>(to + jobs[j].dst);
+            hj[1] = reinterpret_cast<uint64_t>(from + jobs[j].src);
+            hj[2] = jobs[j].len;
+        }
+        hipError_t e = hipMemcpyAsync(dj, pin_jobs.p, bytes, hipMemcpyHostToDevice, s);
         if (e == hipSuccess && first) e = cpk::launch_copy_jobs(dj, first, s);
         if (e == hipSuccess) e = cpk::launch_copy_jobs(dj + 3ull * first, nj - first, s);
-        if (e == hipSuccess && wait) e = hipStreamSynchronize(s);  // `jobs` is reused by the caller
+        if (e == hipSuccess && wait) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "framer copy jobs");
-        if (wait) jobs.clear();
-        else jobs_inflight = true;  // hjobs only: cleared by the next read after settle()
+        if (!wait) jobs_inflight = true;  // until the next synchronisation of s (a walk pass, or settle)
         return CAPNP_PACKED_OK;
     }
-    static uint64_t region_for(uint64_t bytes) { return std::max<uint64_t>(65536, (2 * bytes + 255) & ~255ull); }
-    // A read's region layout, built on copies and committed (commit) only once every copy job
-    // of the read is enqueued: a failed allocation or launch leaves the session as it was.
-    struct Layout {
-        std::vector<uint64_t> off, cap, m0, len;
-        uint64_t top = 0, moved = 0;
-        uint8_t* arena = nullptr;  // a new arena (rearena), freed unless committed
-        uint64_t acap = 0;
-        ~Layout() {
-            if (arena) (void)hipFree(arena);
-        }
-    };
-    void commit(Layout& L) {
-        off.swap(L.off);
-        cap.swap(L.cap);
-        m0.swap(L.m0);
-        len.swap(L.len);
-        top = L.top;
-        moved = L.moved;
-        if (L.arena) {
-            if (arena) (void)hipFree(arena);
-            arena = L.arena;
-            acap = L.acap;
-            L.arena = nullptr;
-        }
-    }
-    // Every connection's live bytes into a new arena (L.arena) with a region sized for want[c]
-    // bytes each; the moves run (and complete) now, from the current arena, which stays valid.
-    int rearena(const std::vector<uint64_t>& want, Layout& L) {
-        uint64_t total = 0;
-        for (uint32_t c = 0; c < n; ++c) total += want[c] ? region_for(want[c]) : 0;
-        const uint64_t ncap = std::max<uint64_t>(2 * total, 1u << 20);
-        uint8_t* na = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&na), ncap + 64);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(framer arena)");
-        L.arena = na;
-        L.acap = ncap;
-        std::vector<uint64_t> jobs;
-        uint64_t t = 0;
-        for (uint32_t c = 0; c < n; ++c) {
-            const uint64_t live = L.len[c] - L.m0[c];
-            if (!want[c]) {
-                L.off[c] = L.cap[c] = L.m0[c] = L.len[c] = 0;
-                continue;
-            }
-            const uint64_t rc = region_for(want[c]);
-            if (live) {
-                jobs.insert(jobs.end(), {reinterpret_cast<uint64_t>(na + t), reinterpret_cast<uint64_t>(arena + L.off[c] + L.m0[c]), live});
-                L.moved += live;
-            }
-            L.off[c] = t;
-            L.cap[c] = rc;
-            L.m0[c] = 0;
-            L.len[c] = live;
-            t += rc;
-        }
-        L.top = t;
-        return run_jobs(jobs);
-    }
+
+    int append(const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, bool staged);
+    int walk_pass(const std::vector<uint32_t>& list);
+    int decode_pass(FramerCall& C);
+    void commit_pass(FramerCall& C);
 };
 
+// Step 1: the read's new bytes, one H2D into the staging buffer (staged: the caller already put
+// them there on the session's stream), appended to the regions by the plan's copy jobs. The
+// layout is committed only once every copy of the read is enqueued: a failed allocation or
+// launch leaves the session as it was.
+int capnp_packed_framer::append(const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off, const uint64_t* in_len,
+                                bool staged) {
+    int st = settle();
+    if (st) return st;
+    if (!in_bytes || !in_len) return CAPNP_PACKED_OK;
+    if (!staged) {
+        if ((st = d_stage.reserve(in_bytes + 32, kSession))) return st;
+        const hipError_t e = hipMemcpyAsync(d_stage.p, in, in_bytes, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(framer H2D)");
+    }
+    framer_layout::Plan P = framer_layout::plan_read(lay, in_off, in_len);
+    const uint32_t nj = (uint32_t)P.jobs.size();
+    if (P.rebuild) {
+        struct NewArena : Buf<false> {  // freed unless committed; then the old arena is, in its place
+            ~NewArena() { release(); }
+        } na;
+        if ((st = na.reserve(P.after.acap + 64, kSessionArena))) return st;
+        // the moves run (and complete) now, from the current arena, which stays valid
+        if ((st = run_jobs(P.jobs.data(), P.first, 0, na.p, true))) return st;
+        if ((st = run_jobs(P.jobs.data() + P.first, nj - P.first, 0, na.p, false))) return st;
+        std::swap(arena, static_cast<Buf<false>&>(na));
+    } else if ((st = run_jobs(P.jobs.data(), nj, P.first, arena.p, false))) {
+        return st;
+    }
+    lay = std::move(P.after);  // every copy of this read is enqueued: the regions describe the arena now
+    uploaded += in_bytes;
+    return CAPNP_PACKED_OK;
+}
+
+// Step 2: one walk over the held bytes of the listed connections, from where each one's last
+// walk stopped. It leaves, page-locked on the host, the connections' need / X / W / status
+// (pin_state, a StateBlock) and the messages found (pin_tab, RoundResults).
+int capnp_packed_framer::walk_pass(const std::vector<uint32_t>& list) {
+    const uint32_t k = (uint32_t)list.size();
+    constexpr uint32_t M = kWalkMessages;
+    const StateBlock h{pin_state.p, n}, d{d_state.p, n};
+    for (uint32_t c = 0; c < n; ++c) {
+        h.base()[c] = lay.off[c] + lay.m0[c];
+        h.avail()[c] = lay.len[c] - lay.m0[c];
+        h.need()[c] = need[c];
+        h.X()[c] = X[c];
+        h.W()[c] = W[c];
+    }
+    int st = d_round.reserve(RoundBlock::device_bytes(k, M), kSession);
+    if (st) return st;
+    const RoundBlock r{d_round.p, k, M};
+    // window tables for the connections whose walk will cross whole windows inside one
+    // message (crossed by lookups): the current message's framed bytes still to walk span
+    // more than two windows, or, with its header not decoded yet, the held bytes span 64
+    // windows. Many small messages end in nearly every window, where a table only costs.
+    const uint64_t wb = cpk::framer_window_bytes(), wcap = cpk::framer_window_cap(k);
+    std::vector<uint32_t> spec32(2ull * k, 0);  // first, count per listed connection
+    std::vector<uint64_t> spec64(2ull * k, 0);  // their bytes: arena offset, length
+    uint64_t T = 0;
+    for (uint32_t j = 0; j < k; ++j) {
+        const uint32_t c = list[j];
+        const uint64_t span = lay.len[c] - lay.m0[c] - X[c];
+        const uint64_t left = need[c] > 8 * W[c] ? need[c] - 8 * W[c] : 0;
+        const bool lookups = need[c] ? left > 2 * wb : span > 64 * wb;
+        uint64_t cnt = lookups && span > wb ? (span + wb - 1) / wb : 0;
+        if (T + cnt > wcap) cnt = 0;
+        spec32[j] = cnt ? (uint32_t)T : 0xFFFFFFFFu;
+        spec32[k + j] = (uint32_t)cnt;
+        spec64[j] = lay.off[c] + lay.m0[c] + X[c];
+        spec64[k + j] = span;
+        T += cnt;
+    }
+    SpecBlock sp(k, T);
+    hipError_t e = hipSuccess;
+    if (T) {
+        if ((st = d_spec.reserve(sp.device_bytes(), kSession))) return st;
+        sp.p = d_spec.p;
+        e = hipMemcpyAsync(sp.windows(), &T, 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sp.first(), spec32.data(), 8ull * k, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sp.off(), spec64.data(), 16ull * k, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return hip_fail(e, "framer window tables");
+    }
+    if ((st = pin_tab.reserve(RoundBlock::results_bytes(k, M), kSessionMeta))) return st;
+    e = hipMemcpyAsync(d.base(), h.base(), h.inputs_bytes(), hipMemcpyHostToDevice, s);
+    std::memcpy(h.list(), list.data(), 4ull * k);
+    if (e == hipSuccess) e = hipMemcpyAsync(r.list(), h.list(), 4ull * k, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = cpk::launch_frame_walk(arena.p, r.list(), k, d.base(), d.avail(), d.need(), d.X(), d.W(), d.status(), M,
+                                   r.counts(), r.table(), sp.queue(), T, sp.first(), sp.count(), sp.off(), sp.len(), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.need(), d.need(), h.results_bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(pin_tab.p, r.counts(), RoundBlock::results_bytes(k, M), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "framer walk pass");
+    jobs_inflight = false;
+    ++walk_passes;
+    table_windows += T;
+    return CAPNP_PACKED_OK;
+}
+
+// Step 3: the whole messages the walk found, in order per connection, while the frames buffer
+// and table hold them: decoded from the arena into frame slots, then to the caller's buffer.
+int capnp_packed_framer::decode_pass(FramerCall& C) {
+    const uint32_t k = (uint32_t)C.list.size();
+    const StateBlock h{pin_state.p, n};
+    const RoundResults found{reinterpret_cast<const uint32_t*>(pin_tab.p), k, kWalkMessages};
+    C.um.clear();
+    C.uconn.clear();
+    C.slots = 0;
+    for (uint32_t j = 0; j < k; ++j) {
+        const uint32_t c = C.list[j];
+        const uint32_t* const tj = found.messages(j);
+        uint64_t at = 0;
+        uint32_t m = 0;
+        for (; m < found.count(j); ++m) {
+            const uint64_t L = tj[2 * m + 1];
+            if (C.nf + C.uconn.size() + 1 > C.max_frames || C.fcur + C.slots + L > C.frames_cap) {
+                C.full = true;  // stays whole in its region: the next call pops it
+                break;
+            }
+            C.um.insert(C.um.end(), {lay.off[c] + lay.m0[c] + at, tj[2 * m], C.slots, L});
+            C.uconn.push_back(c);
+            C.slots += (L + 7) & ~7ull;
+            at += tj[2 * m];
+        }
+        C.adv[c] = at;
+        C.perr[c] = CAPNP_PACKED_OK;
+        C.more[c] = 0;
+        if (m < found.count(j)) {  // the frames ran out: message m stays found whole (X at its end)
+            h.need()[c] = tj[2 * m + 1];
+            h.X()[c] = tj[2 * m];
+            h.W()[c] = tj[2 * m + 1] / 8;
+        } else if (h.status()[c] == CAPNP_PACKED_OK) {
+            C.more[c] = 1;  // M messages: the next pass walks on from the last one's end
+        } else if (h.status()[c] != CAPNP_PACKED_END_OF_STREAM) {
+            C.perr[c] = h.status()[c];
+        }
+    }
+    const uint32_t U = (uint32_t)C.uconn.size();
+    if (!U) return CAPNP_PACKED_OK;
+    int st;
+    if ((st = d_frames.reserve(C.slots + 16, kSession))) return st;
+    if ((st = d_units.reserve(UnitBlock::device_bytes(U), kSession))) return st;
+    if ((st = pin_units.reserve(UnitBlock::host_bytes(U), kSessionMeta))) return st;
+    const UnitBlock u{{reinterpret_cast<uint64_t*>(d_units.p), U}}, hu{{reinterpret_cast<uint64_t*>(pin_units.p), U}};
+    for (uint32_t q = 0; q < U; ++q)
+        for (uint32_t a = 0; a < 4; ++a) hu.col(a)[q] = C.um[4ull * q + a];
+    hipError_t e = hipMemcpyAsync(u.p, hu.p, hu.inputs_bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = cpk::launch_decode(arena.p, u.in_off(), u.in_len(), U, d_frames.p, u.out_off(), u.out_cap(), u.out_len(),
+                               u.status(), true, nullptr, 0, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(C.frames + C.fcur, d_frames.p, C.slots, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hu.out_len(), u.out_len(), hu.results_bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "framer decode pass");
+    for (uint32_t q = 0; q < U; ++q) {
+        if (hu.status()[q] != CAPNP_PACKED_OK || hu.out_len()[q] != hu.out_cap()[q])  // the walk verified the bytes
+            return fail(CAPNP_PACKED_DEVICE_ERROR, "framer: a walked message did not decode to its framed length");
+        C.frame_off[C.nf] = C.fcur + hu.out_off()[q];
+        C.frame_len[C.nf] = hu.out_cap()[q];
+        C.frame_conn[C.nf] = C.uconn[q];
+        ++C.nf;
+    }
+    C.fcur += C.slots;
+    return CAPNP_PACKED_OK;
+}
+
+// Step 4a: the pass's connections take their new state; an error is reported after the frames
+// before it, and Connection.handleRead resets the framer on it (connection.zig:175-184).
+void capnp_packed_framer::commit_pass(FramerCall& C) {
+    const StateBlock h{pin_state.p, n};
+    for (const uint32_t c : C.list) {
+        lay.m0[c] += C.adv[c];
+        need[c] = h.need()[c];
+        X[c] = h.X()[c];
+        W[c] = h.W()[c];
+        if (C.perr[c] == CAPNP_PACKED_OK) continue;
+        C.status[c] = C.perr[c];
+        C.dead[c] = 1;
+        lay.m0[c] = lay.len[c] = 0;
+        need[c] = X[c] = W[c] = 0;
+    }
+}
+
 namespace {
+
+// capnp_packed_framer_read with f->mu held and its arguments checked: the new bytes, then passes
+// (a walk over every connection's held messages, one decode of them) until no connection holds
+// a whole message or the caller's frames are full.
+int framer_read_locked(capnp_packed_framer* f, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
+                       const uint64_t* in_len, bool staged, FramerCall& C, uint32_t* n_frames) {
+    const uint32_t n = f->n;
+    for (uint32_t c = 0; c < n; ++c) C.status[c] = CAPNP_PACKED_END_OF_STREAM;
+    int st = f->append(in, in_bytes, in_off, in_len, staged);
+    if (st) return st;
+    if ((st = f->d_state.reserve(StateBlock::device_bytes(n, 0), kSession))) return st;  // see StateBlock
+    if ((st = f->pin_state.reserve(StateBlock::host_bytes(n), kSessionMeta))) return st;
+    C.dead.assign(n, 0);
+    C.more.resize(n);
+    C.adv.resize(n);
+    C.perr.resize(n);
+    for (uint32_t c = 0; c < n; ++c) C.more[c] = f->lay.len[c] > f->lay.m0[c];
+    while (!C.full) {
+        C.list.clear();
+        for (uint32_t c = 0; c < n; ++c)
+            if (!C.dead[c] && C.more[c]) C.list.push_back(c);
+        if (C.list.empty()) break;
+        if ((st = f->walk_pass(C.list))) return st;
+        if ((st = f->decode_pass(C))) return st;
+        f->commit_pass(C);
+    }
+    *n_frames = C.nf;
+    if ((st = f->settle())) return st;  // no pass ran after the upload: the caller's bytes are consumed
+    return C.full ? fail(CAPNP_PACKED_OUT_OF_SPACE, "frames buffer or frame table full: call again to pop the rest")
+                  : CAPNP_PACKED_OK;
+}
 
 int framer_check(capnp_packed_framer* f, uint32_t conn) {
     if (!f) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "framer is null");
     if (conn >= f->n) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "connection index out of range");
     return CAPNP_PACKED_OK;
 }
-
-}  // namespace
-
-extern "C" {
-
-int capnp_packed_framer_create(uint32_t n_conns, capnp_packed_framer** out) {
-    if (!out) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out is null");
-    *out = nullptr;
-    if (n_conns == 0) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a framer needs at least one connection");
-    int st = ensure_device();
-    if (st) return st;
-    capnp_packed_framer* f = new (std::nothrow) capnp_packed_framer();
-    if (!f) return fail(CAPNP_PACKED_OUT_OF_SPACE, "framer allocation");
-    f->n = n_conns;
-    if (hipGetDevice(&f->dev) != hipSuccess) f->dev = -1;
-    for (auto* v : {&f->off, &f->cap, &f->m0, &f->len, &f->need, &f->X, &f->W}) v->assign(n_conns, 0);
-    hipError_t e = hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        f->s = nullptr;
-        delete f;
-        return hip_fail(e, "hipStreamCreate(framer session)");
-    }
-    *out = f;
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_destroy(capnp_packed_framer* f) {
-    if (!f) return CAPNP_PACKED_OK;
-    delete f;  // synchronises its stream first
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_reset(capnp_packed_framer* f, uint32_t conn) {
-    int st = framer_check(f, conn);
-    if (st) return st;
-    std::lock_guard<std::mutex> lock(f->mu);
-    f->m0[conn] = f->len[conn] = 0;
-    f->need[conn] = f->X[conn] = f->W[conn] = 0;
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_buffered(capnp_packed_framer* f, uint32_t conn, uint64_t* bytes) {
-    int st = framer_check(f, conn);
-    if (st) return st;
-    if (!bytes) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bytes is null");
-    std::lock_guard<std::mutex> lock(f->mu);
-    *bytes = f->len[conn] - f->m0[conn];
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_expected(capnp_packed_framer* f, uint32_t conn, uint64_t* framed_bytes) {
-    int st = framer_check(f, conn);
-    if (st) return st;
-    if (!framed_bytes) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "framed_bytes is null");
-    std::lock_guard<std::mutex> lock(f->mu);
-    *framed_bytes = f->need[conn];
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_stats(capnp_packed_framer* f, uint64_t* uploaded, uint64_t* moved) {
-    if (!f || !uploaded || !moved) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null pointer");
-    std::lock_guard<std::mutex> lock(f->mu);
-    *uploaded = f->uploaded;
-    *moved = f->moved;
-    return CAPNP_PACKED_OK;
-}
-
-int capnp_packed_framer_walk_stats(capnp_packed_framer* f, uint64_t* passes, uint64_t* table_windows) {
-    if (!f || !passes || !table_windows) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null pointer");
-    std::lock_guard<std::mutex> lock(f->mu);
-    *passes = f->walk_passes;
-    *table_windows = f->table_windows;
-    return CAPNP_PACKED_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
 
 // The gather of capnp_packed_framer_readv: bytes [r0, r1) of the connections' reads, laid end
 // to end at their prefix offsets, into the session's page-locked staging, by byte range over up
@@ -1097,288 +1267,79 @@ int framer_args(capnp_packed_framer* f, uint8_t* frames, uint64_t frames_cap, ui
     return CAPNP_PACKED_OK;
 }
 
-// capnp_packed_framer_read with f->mu held and its arguments checked
-// (staged: the caller already put the input's bytes into d_stage on the session's stream)
-int framer_read_locked(capnp_packed_framer* f, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
-                       const uint64_t* in_len, uint8_t* frames, uint64_t frames_cap, uint64_t* frame_off,
-                       uint64_t* frame_len, uint32_t* frame_conn, uint32_t max_frames, int32_t* status,
-                       uint32_t* n_frames, bool staged = false) {
-    const uint32_t n = f->n;
-    const hipStream_t s = f->s;
-    hipError_t e = hipSuccess;
-    int st = CAPNP_PACKED_OK;
-    for (uint32_t c = 0; c < n; ++c) status[c] = CAPNP_PACKED_END_OF_STREAM;
-
-    // ---- 1. the new bytes: one H2D into the staging buffer, appended to the regions ---------
-    if ((st = f->settle())) return st;  // a previous read's copies are done with d_stage / hjobs
-    if (in_bytes && in_len) {
-        if (!staged) {
-            if ((st = capnp_packed_framer::grow(&f->d_stage, &f->stage_cap, in_bytes + 32))) return st;
-            e = hipMemcpyAsync(f->d_stage, in, in_bytes, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(framer H2D)");
-        }
-        // regions: a connection whose bytes would pass its region's end slides its held bytes to
-        // the region's start when they and the new bytes fit there and the slide's source and
-        // target do not overlap (held <= m0; a drained connection just restarts there), else it
-        // gets a new region. The slides run as a launch of their own before the appends, which may
-        // overwrite their source.
-        auto slides = [&](uint32_t c) {
-            const uint64_t held = f->len[c] - f->m0[c];
-            return in_len[c] && f->len[c] + in_len[c] > f->cap[c] && held + in_len[c] <= f->cap[c] && held <= f->m0[c];
-        };  // (on the session's layout, before this read)
-        std::vector<uint64_t> want(n, 0);
-        uint64_t grow_bytes = 0;
-        bool any_grow = false;
-        for (uint32_t c = 0; c < n; ++c) {
-            const uint64_t live = f->len[c] - f->m0[c] + in_len[c];
-            want[c] = live;
-            if (in_len[c] && f->len[c] + in_len[c] > f->cap[c] && !slides(c)) {
-                any_grow = true;
-                grow_bytes += capnp_packed_framer::region_for(live);
-            }
-        }
-        capnp_packed_framer::Layout L;  // the session's layout after this read, committed below
-        L.off = f->off;
-        L.cap = f->cap;
-        L.m0 = f->m0;
-        L.len = f->len;
-        L.top = f->top;
-        L.moved = f->moved;
-        std::vector<uint64_t>& jobs = f->hjobs;
-        jobs.clear();
-        uint32_t n_slides = 0;
-        if (any_grow && f->top + grow_bytes > f->acap) {
-            if ((st = f->rearena(want, L))) return st;  // every region sized for its bytes after this read
-        } else {
-            for (uint32_t c = 0; c < n; ++c) {
-                if (!slides(c)) continue;
-                const uint64_t held = L.len[c] - L.m0[c];
-                if (held) {
-                    jobs.insert(jobs.end(), {reinterpret_cast<uint64_t>(f->arena + L.off[c]),
-                                             reinterpret_cast<uint64_t>(f->arena + L.off[c] + L.m0[c]), held});
-                    L.moved += held;
-                    ++n_slides;
-                }
-                L.m0[c] = 0;
-                L.len[c] = held;
-            }
-            for (uint32_t c = 0; any_grow && c < n; ++c) {  // the slid ones fit now
-                if (!in_len[c] || L.len[c] + in_len[c] <= L.cap[c]) continue;
-                const uint64_t live = L.len[c] - L.m0[c];
-                const uint64_t rc = capnp_packed_framer::region_for(want[c]);
-                if (live) {
-                    jobs.insert(jobs.end(), {reinterpret_cast<uint64_t>(f->arena + L.top),
-                                             reinterpret_cast<uint64_t>(f->arena + L.off[c] + L.m0[c]), live});
-                    L.moved += live;
-                }
-                L.off[c] = L.top;
-                L.cap[c] = rc;
-                L.m0[c] = 0;
-                L.len[c] = live;
-                L.top += rc;
-            }
-        }
-        for (uint32_t c = 0; c < n; ++c) {
-            if (!in_len[c]) continue;
-            jobs.insert(jobs.end(), {reinterpret_cast<uint64_t>((L.arena ? L.arena : f->arena) + L.off[c] + L.len[c]),
-                                     reinterpret_cast<uint64_t>(f->d_stage + in_off[c]), in_len[c]});
-            L.len[c] += in_len[c];
-        }
-        if ((st = f->run_jobs(jobs, false, n_slides))) return st;  // ordered before the passes below
-        f->commit(L);  // every copy of this read is enqueued: the regions describe the arena now
-        f->uploaded += in_bytes;
-    }
-
-    // ---- 2. passes: a walk over every connection's held messages, then one decode of them ----
-    // state scratch: base, avail, need, X, W (u64 x n), status (i32 x n), then the copy jobs
-    // (run_jobs) past them; the pass's list / counts / message table and the decode metadata
-    // live in blocks of their own
-    if ((st = capnp_packed_framer::grow(&f->d_state, &f->state_cap, (uint64_t)n * 56 + 256 + 64ull * n + 4096))) return st;
-    uint64_t* const d_base = reinterpret_cast<uint64_t*>(f->d_state);
-    uint64_t* const d_avail = d_base + n;
-    uint64_t* const d_need = d_base + 2ull * n;
-    uint64_t* const d_X = d_base + 3ull * n;
-    uint64_t* const d_W = d_base + 4ull * n;
-    int32_t* const d_st = reinterpret_cast<int32_t*>(d_base + 6ull * n);
-    constexpr uint32_t M = capnp_packed_framer::kWalkMessages;
-    if ((st = f->pin_state.reserve(60ull * n))) return st;  // 7 u64 then the pass's list (u32) per connection
-    uint64_t* const h = reinterpret_cast<uint64_t*>(f->pin_state.p);  // base, avail, need, X, W, (free), status (i32)
-    std::vector<uint32_t> spec_h;    // window tables' first / count per listed connection
-    std::vector<uint64_t> spec_h64;  // their bytes: arena offset, length
-    uint64_t spec_T = 0;
-    const int32_t* const hst = reinterpret_cast<const int32_t*>(h + 6ull * n);
-    std::vector<uint32_t> list;
-    std::vector<uint8_t> dead(n, 0), more(n, 0);  // dead: an error this call (the connection was reset)
-    std::vector<uint64_t> adv(n), um;             // adv: packed bytes of the pass's accepted messages
-    std::vector<uint32_t> uconn;                  // the pass's accepted messages: connection
-    std::vector<int32_t> perr(n);                 // an error to report once the pass's frames are out
-    for (uint32_t c = 0; c < n; ++c) more[c] = f->len[c] > f->m0[c];
-    uint64_t fcur = 0;
-    uint32_t nf = 0;
-    auto fail_conn = [&](uint32_t c, int32_t code) {
-        status[c] = code;
-        dead[c] = 1;
-        f->m0[c] = f->len[c] = 0;  // Connection.handleRead resets the framer (connection.zig:175-184)
-        f->need[c] = f->X[c] = f->W[c] = 0;
-    };
-    bool full = false;
-    while (!full) {
-        list.clear();
-        for (uint32_t c = 0; c < n; ++c)
-            if (!dead[c] && more[c]) list.push_back(c);
-        uint32_t k = (uint32_t)list.size();
-        if (k == 0) break;
-        for (uint32_t c = 0; c < n; ++c) {
-            h[c] = f->off[c] + f->m0[c];
-            h[n + c] = f->len[c] - f->m0[c];
-            h[2ull * n + c] = f->need[c];
-            h[3ull * n + c] = f->X[c];
-            h[4ull * n + c] = f->W[c];
-        }
-        const uint64_t tab_words = 2ull * k * M;
-        if ((st = capnp_packed_framer::grow(&f->d_round, &f->round_cap, 4ull * (2ull * k + tab_words) + 256))) return st;
-        uint32_t* const r_list = reinterpret_cast<uint32_t*>(f->d_round);
-        uint32_t* const r_cnt = r_list + k;
-        uint32_t* const r_tab = r_cnt + k;
-        // window tables for the connections whose walk will cross whole windows inside one
-        // message (crossed by lookups): the current message's framed bytes still to walk span
-        // more than two windows, or, with its header not decoded yet, the held bytes span 64
-        // windows. Many small messages end in nearly every window, where a table only costs.
-        const uint64_t wb = cpk::framer_window_bytes(), wcap = cpk::framer_window_cap(k);
-        spec_h.assign(2ull * k, 0);  // first, count per listed connection (u32); off, len (u64) below
-        spec_h64.assign(2ull * k, 0);
-        uint64_t T = 0;
-        for (uint32_t j = 0; j < k; ++j) {
-            const uint32_t c = list[j];
-            const uint64_t span = f->len[c] - f->m0[c] - f->X[c];
-            const uint64_t left = f->need[c] > 8 * f->W[c] ? f->need[c] - 8 * f->W[c] : 0;
-            const bool lookups = f->need[c] ? left > 2 * wb : span > 64 * wb;
-            uint64_t cnt = lookups && span > wb ? (span + wb - 1) / wb : 0;
-            if (T + cnt > wcap) cnt = 0;
-            spec_h[j] = cnt ? (uint32_t)T : 0xFFFFFFFFu;
-            spec_h[k + j] = (uint32_t)cnt;
-            spec_h64[j] = f->off[c] + f->m0[c] + f->X[c];
-            spec_h64[k + j] = span;
-            T += cnt;
-        }
-        uint32_t* d_sq = nullptr;
-        const uint32_t *d_sfirst = nullptr, *d_scount = nullptr;
-        const uint64_t *d_soff = nullptr, *d_slen = nullptr;
-        if (T) {
-            const uint64_t qb = (cpk::framer_spec_bytes(k, T) + 15) & ~15ull;
-            const uint64_t ab = (8ull * k + 15) & ~15ull;
-            if ((st = capnp_packed_framer::grow(&f->d_spec, &f->spec_cap, qb + ab + 16ull * k + 64))) return st;
-            d_sq = reinterpret_cast<uint32_t*>(f->d_spec);
-            uint32_t* const a32 = reinterpret_cast<uint32_t*>(f->d_spec + qb);
-            uint64_t* const a64 = reinterpret_cast<uint64_t*>(f->d_spec + qb + ab);
-            d_sfirst = a32;
-            d_scount = a32 + k;
-            d_soff = a64;
-            d_slen = a64 + k;
-            spec_T = T;
-            e = hipMemcpyAsync(d_sq + 8, &spec_T, 8, hipMemcpyHostToDevice, s);  // q_tiles: the windows
-            if (e == hipSuccess) e = hipMemcpyAsync(a32, spec_h.data(), 8ull * k, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(a64, spec_h64.data(), 16ull * k, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return hip_fail(e, "framer window tables");
-        }
-        if ((st = f->pin_tab.reserve(4ull * (k + tab_words)))) return st;
-        const uint32_t* const hcnt = reinterpret_cast<const uint32_t*>(f->pin_tab.p);  // counts, then the table
-        e = hipMemcpyAsync(d_base, h, 5ull * n * 8, hipMemcpyHostToDevice, s);
-        uint32_t* const plist = reinterpret_cast<uint32_t*>(f->pin_state.p + 56ull * n);
-        std::memcpy(plist, list.data(), 4ull * k);
-        if (e == hipSuccess) e = hipMemcpyAsync(r_list, plist, 4ull * k, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = cpk::launch_frame_walk(f->arena, r_list, k, d_base, d_avail, d_need, d_X, d_W, d_st, M, r_cnt, r_tab,
-                                       d_sq, T, d_sfirst, d_scount, d_soff, d_slen, s);
-        // need, X, W, (a free slot), status: one copy; the counts and the table: another
-        if (e == hipSuccess) e = hipMemcpyAsync(h + 2ull * n, d_need, 3ull * n * 8 + n * 8 + 4ull * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(f->pin_tab.p, r_cnt, 4ull * (k + tab_words), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "framer walk pass");
-        f->jobs_inflight = false;
-        ++f->walk_passes;
-        f->table_windows += T;
-        // whole messages, in order per connection, while the frames buffer and table hold them:
-        // decoded from the arena into frame slots, then to the caller's buffer
-        um.clear();  // per message: in_off, in_len, out_off, out_cap
-        uconn.clear();
-        uint64_t slots = 0;
-        for (uint32_t j = 0; j < k; ++j) {
-            const uint32_t c = list[j];
-            const uint32_t* const tj = hcnt + k + 2ull * j * M;
-            uint64_t at = 0;
-            uint32_t m = 0;
-            for (; m < hcnt[j]; ++m) {
-                const uint64_t L = tj[2 * m + 1];
-                if (nf + uconn.size() + 1 > max_frames || fcur + slots + L > frames_cap) {
-                    full = true;  // stays whole in its region: the next call pops it
-                    break;
-                }
-                um.insert(um.end(), {f->off[c] + f->m0[c] + at, tj[2 * m], slots, L});
-                uconn.push_back(c);
-                slots += (L + 7) & ~7ull;
-                at += tj[2 * m];
-            }
-            adv[c] = at;
-            perr[c] = CAPNP_PACKED_OK;
-            more[c] = 0;
-            if (m < hcnt[j]) {  // the frames ran out: message m stays found whole (X at its end)
-                h[2ull * n + c] = tj[2 * m + 1];
-                h[3ull * n + c] = tj[2 * m];
-                h[4ull * n + c] = tj[2 * m + 1] / 8;
-            } else if (hst[c] == CAPNP_PACKED_OK) {
-                more[c] = 1;  // M messages: the next pass walks on from the last one's end
-            } else if (hst[c] != CAPNP_PACKED_END_OF_STREAM) {
-                perr[c] = hst[c];
-            }
-        }
-        const uint32_t U = (uint32_t)uconn.size();
-        if (U) {
-            if ((st = capnp_packed_framer::grow(&f->d_frames, &f->frames_dcap, slots + 16))) return st;
-            if ((st = capnp_packed_framer::grow(&f->d_units, &f->units_cap, 48ull * U + 64))) return st;
-            uint64_t* const u = reinterpret_cast<uint64_t*>(f->d_units);
-            if ((st = f->pin_units.reserve(48ull * U))) return st;
-            uint64_t* const hm = reinterpret_cast<uint64_t*>(f->pin_units.p);
-            for (uint32_t q = 0; q < U; ++q)
-                for (uint32_t a = 0; a < 4; ++a) hm[a * (uint64_t)U + q] = um[4ull * q + a];
-            e = hipMemcpyAsync(u, hm, 4ull * U * 8, hipMemcpyHostToDevice, s);
-            int32_t* const u_st = reinterpret_cast<int32_t*>(u + 5ull * U);
-            if (e == hipSuccess)
-                e = cpk::launch_decode(f->arena, u, u + U, U, f->d_frames, u + 2ull * U, u + 3ull * U, u + 4ull * U,
-                                       u_st, true, nullptr, 0, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(frames + fcur, f->d_frames, slots, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(hm + 4ull * U, u + 4ull * U, 2ull * U * 8, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return hip_fail(e, "framer decode pass");
-            const int32_t* const us = reinterpret_cast<const int32_t*>(hm + 5ull * U);
-            for (uint32_t q = 0; q < U; ++q) {
-                if (us[q] != CAPNP_PACKED_OK || hm[4ull * U + q] != hm[3ull * U + q])  // the walk verified the bytes
-                    return fail(CAPNP_PACKED_DEVICE_ERROR, "framer: a walked message did not decode to its framed length");
-                frame_off[nf] = fcur + hm[2ull * U + q];
-                frame_len[nf] = hm[3ull * U + q];
-                frame_conn[nf] = uconn[q];
-                ++nf;
-            }
-            fcur += slots;
-        }
-        for (uint32_t j = 0; j < k; ++j) {
-            const uint32_t c = list[j];
-            f->m0[c] += adv[c];
-            f->need[c] = h[2ull * n + c];
-            f->X[c] = h[3ull * n + c];
-            f->W[c] = h[4ull * n + c];
-            if (perr[c] != CAPNP_PACKED_OK) fail_conn(c, perr[c]);  // after the frames before it
-        }
-    }
-    *n_frames = nf;
-    if ((st = f->settle())) return st;  // no pass ran after the upload: the caller's bytes are consumed
-    return full ? fail(CAPNP_PACKED_OUT_OF_SPACE, "frames buffer or frame table full: call again to pop the rest")
-                : CAPNP_PACKED_OK;
-}
-
 }  // namespace
 
 extern "C" {
+
+int capnp_packed_framer_create(uint32_t n_conns, capnp_packed_framer** out) {
+    if (!out) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out is null");
+    *out = nullptr;
+    if (n_conns == 0) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a framer needs at least one connection");
+    int st = ensure_device();
+    if (st) return st;
+    capnp_packed_framer* f = new (std::nothrow) capnp_packed_framer();
+    if (!f) return fail(CAPNP_PACKED_OUT_OF_SPACE, "framer allocation");
+    f->n = n_conns;
+    if (hipGetDevice(&f->dev) != hipSuccess) f->dev = -1;
+    for (auto* v : {&f->lay.off, &f->lay.cap, &f->lay.m0, &f->lay.len, &f->need, &f->X, &f->W}) v->assign(n_conns, 0);
+    hipError_t e = hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        f->s = nullptr;
+        delete f;
+        return hip_fail(e, "hipStreamCreate(framer session)");
+    }
+    *out = f;
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_destroy(capnp_packed_framer* f) {
+    if (!f) return CAPNP_PACKED_OK;
+    delete f;  // synchronises its stream first
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_reset(capnp_packed_framer* f, uint32_t conn) {
+    int st = framer_check(f, conn);
+    if (st) return st;
+    std::lock_guard<std::mutex> lock(f->mu);
+    f->lay.m0[conn] = f->lay.len[conn] = 0;
+    f->need[conn] = f->X[conn] = f->W[conn] = 0;
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_buffered(capnp_packed_framer* f, uint32_t conn, uint64_t* bytes) {
+    int st = framer_check(f, conn);
+    if (st) return st;
+    if (!bytes) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bytes is null");
+    std::lock_guard<std::mutex> lock(f->mu);
+    *bytes = f->lay.len[conn] - f->lay.m0[conn];
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_expected(capnp_packed_framer* f, uint32_t conn, uint64_t* framed_bytes) {
+    int st = framer_check(f, conn);
+    if (st) return st;
+    if (!framed_bytes) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "framed_bytes is null");
+    std::lock_guard<std::mutex> lock(f->mu);
+    *framed_bytes = f->need[conn];
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_stats(capnp_packed_framer* f, uint64_t* uploaded, uint64_t* moved) {
+    if (!f || !uploaded || !moved) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null pointer");
+    std::lock_guard<std::mutex> lock(f->mu);
+    *uploaded = f->uploaded;
+    *moved = f->lay.moved;
+    return CAPNP_PACKED_OK;
+}
+
+int capnp_packed_framer_walk_stats(capnp_packed_framer* f, uint64_t* passes, uint64_t* table_windows) {
+    if (!f || !passes || !table_windows) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null pointer");
+    std::lock_guard<std::mutex> lock(f->mu);
+    *passes = f->walk_passes;
+    *table_windows = f->table_windows;
+    return CAPNP_PACKED_OK;
+}
 
 int capnp_packed_framer_read(capnp_packed_framer* f, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
                              const uint64_t* in_len, uint8_t* frames, uint64_t frames_cap, uint64_t* frame_off,
@@ -1393,8 +1354,8 @@ int capnp_packed_framer_read(capnp_packed_framer* f, const uint8_t* in, uint64_t
             if (in_len[c] && (!in_off || in_off[c] > in_bytes || in_len[c] > in_bytes - in_off[c]))
                 return fail(CAPNP_PACKED_INVALID_ARGUMENT, "connection bytes outside the input buffer");
     std::lock_guard<std::mutex> lock(f->mu);
-    return framer_read_locked(f, in, in_bytes, in_off, in_len, frames, frames_cap, frame_off, frame_len, frame_conn,
-                              max_frames, status, n_frames);
+    FramerCall C{frames, frames_cap, frame_off, frame_len, frame_conn, max_frames, status};
+    return framer_read_locked(f, in, in_bytes, in_off, in_len, false, C, n_frames);
 }
 
 int capnp_packed_framer_readv(capnp_packed_framer* f, const uint8_t* const* in_ptr, const uint64_t* in_len,
@@ -1414,32 +1375,22 @@ int capnp_packed_framer_readv(capnp_packed_framer* f, const uint8_t* const* in_p
     std::lock_guard<std::mutex> lock(f->mu);
     if (total) {
         // the previous call's upload from the staging has finished (each call ends synchronised)
-        if (!f->h_stage || f->h_stage_cap < total) {
-            if (f->h_stage) (void)hipHostFree(f->h_stage);
-            f->h_stage = nullptr;
-            f->h_stage_cap = 0;
-            const uint64_t want = std::max<uint64_t>(total + total / 4, 1u << 20);
-            hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&f->h_stage), want, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                f->h_stage = nullptr;
-                return hip_fail(e, "hipHostMalloc(framer staging)");
-            }
-            f->h_stage_cap = want;
-        }
+        if ((st = f->h_stage.reserve(total, kSessionStaging))) return st;
         // gather and upload in 32-MiB pieces: piece i's H2D runs while piece i + 1 is gathered
         if ((st = f->settle())) return st;  // the previous read's copies are done with d_stage
-        if ((st = capnp_packed_framer::grow(&f->d_stage, &f->stage_cap, total + 32))) return st;
+        if ((st = f->d_stage.reserve(total + 32, kSession))) return st;
         constexpr uint64_t kPiece = 32ull << 20;
         for (uint64_t r0 = 0; r0 < total; r0 += kPiece) {
             const uint64_t r1 = std::min(total, r0 + kPiece);
-            gather_reads(f->h_stage, in_ptr, in_len, off.data(), n, r0, r1);
-            const hipError_t e = hipMemcpyAsync(f->d_stage + r0, f->h_stage + r0, r1 - r0, hipMemcpyHostToDevice, f->s);
+            gather_reads(f->h_stage.p, in_ptr, in_len, off.data(), n, r0, r1);
+            const hipError_t e =
+                hipMemcpyAsync(f->d_stage.p + r0, f->h_stage.p + r0, r1 - r0, hipMemcpyHostToDevice, f->s);
             if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(framer H2D)");
         }
     }
-    return framer_read_locked(f, total ? f->h_stage : nullptr, total, total ? off.data() : nullptr,
-                              total ? in_len : nullptr, frames, frames_cap, frame_off, frame_len, frame_conn,
-                              max_frames, status, n_frames, true);
+    FramerCall C{frames, frames_cap, frame_off, frame_len, frame_conn, max_frames, status};
+    return framer_read_locked(f, total ? f->h_stage.p : nullptr, total, total ? off.data() : nullptr,
+                              total ? in_len : nullptr, true, C, n_frames);
 }
 
 }  // extern "C"

@@ -171,3 +171,33 @@ def test_one_kernel_paths_around_their_limits():
         assert cp.pack_packed(data) == oracle.pack(data)[1], nbytes
     with pytest.raises(cp.InvalidMessageSize):
         cp.pack_packed(bytes(4092))
+
+
+def test_workspaces_above_64_mib_are_given_back_and_regrown():
+    """The single-buffer context's reallocation paths. 49,152 `00 FF` records (98,304 packed
+    bytes, 96 MiB of zeros): the first device slot is 8 n, so the call retries from the input
+    already on the device with a slot of the reported size and then holds an output workspace
+    and staging above 64 MiB. A 1-KiB unit's encode and decode need under a quarter of them, so
+    both are given back and allocated small. The 96 MiB decode again grows them again."""
+    L = cp.lib()
+    records, zeros_bytes = 49152, 49152 * 2048
+    packed = bytes([0x00, 0xFF]) * records
+    out = np.empty(zeros_bytes, dtype=np.uint8)
+    small = message(1024, 128, seed=0xC0DE0B70)
+    _, small_packed = oracle.pack(small)
+
+    def decode_zeros():
+        out.fill(0xAB)
+        n = ctypes.c_size_t(7)
+        st = L.capnp_packed_decode(packed, len(packed), out.ctypes.data, out.size, ctypes.byref(n))
+        assert (st, n.value) == (cp.OK, zeros_bytes)
+        assert not np.any(out)
+
+    decode_zeros()
+    buf = ctypes.create_string_buffer(cp.encode_bound(len(small)))
+    n = ctypes.c_size_t(7)
+    assert L.capnp_packed_encode(small, len(small), buf, len(buf), ctypes.byref(n)) == cp.OK
+    assert n.value == len(small_packed) and buf.raw[:n.value] == small_packed
+    st, n, got = decode_raw(small_packed, len(small))
+    assert (st, n) == (cp.OK, len(small)) and got == small
+    decode_zeros()
