@@ -137,7 +137,9 @@ int capnp_packed_decode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, s
  *
  * Word-side alignment: the unpacked side of every unit (encode input, decode
  * output) must start at a multiple of 8 bytes (INVALID_ARGUMENT otherwise); the
- * packed side may start anywhere (dense packed streams are supported).
+ * packed side may start anywhere (dense packed streams are supported). An empty encode
+ * unit whose input offset is misaligned is INVALID_ARGUMENT too (out_len 0, nothing
+ * written), while an empty decode unit is OK whatever its slot's alignment.
  *
  * `stream` is a hipStream_t (NULL = default stream). Calls are asynchronous:
  * they enqueue kernels and return. The return value reports launch errors only;

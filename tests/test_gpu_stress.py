@@ -156,6 +156,7 @@ def test_encode_batch_stress():
         if len(exp) <= caps[i]:
             assert (int(pst[i]), int(plen[i])) == (0, len(exp)), i
             assert out[ooff[i]:ooff[i] + len(exp)].tobytes() == exp, i
+            assert (out[ooff[i] + len(exp):ooff[i] + caps[i]] == CANARY).all(), ("bytes past out_len written", i)
         else:
             assert (int(pst[i]), int(plen[i])) == (cp.OUT_OF_SPACE, len(exp)), i
     assert (out[~covered] == CANARY).all()
