@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "capnp_packed.h"
+#include "class_ws.h"
 #include "framer_layout.h"
 #include "kernels.h"
 
@@ -229,7 +230,7 @@ struct RoundResults {
 };
 
 // The window tables of a walk pass over k connections with T windows in all: the tables' queue
-// (cpk::framer_spec_bytes; its u64 at u32 index 8 is T), then per listed connection the first
+// (cpk::framer_spec_bytes; its u64 at u32 index cpk::kSlotReserved is T), then per listed connection the first
 // window and the count (u32), then its bytes' arena offset and length (u64). A pass without
 // tables has p null, and every part of the block is null with it.
 struct SpecBlock {
@@ -241,7 +242,7 @@ struct SpecBlock {
     template <class T>
     T* at(uint64_t byte, uint64_t i) const { return p ? reinterpret_cast<T*>(p + byte) + i : nullptr; }
     uint32_t* queue() const { return at<uint32_t>(0, 0); }
-    uint32_t* windows() const { return at<uint32_t>(0, 8); }
+    uint32_t* windows() const { return at<uint32_t>(0, cpk::kSlotReserved); }
     uint32_t* first() const { return at<uint32_t>(qb, 0); }
     uint32_t* count() const { return at<uint32_t>(qb, k); }
     uint64_t* off() const { return at<uint64_t>(qb + ab, 0); }

@@ -8,8 +8,8 @@
 namespace cpk {
 
 // Batch encode / decode (write = false: sizes only). ws: optional caller workspace of
-// at least queue_bytes(n) bytes for the long-unit queue (nullptr: the caller stream's
-// own queue, kept by the library).
+// at least queue_bytes(n) bytes for the batch's class workspace (class_ws.h; nullptr: the
+// caller stream's own workspace, kept by the library).
 hipError_t launch_encode(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                          uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
                          int32_t* status, bool write, void* ws, size_t ws_bytes, hipStream_t stream);
@@ -49,8 +49,8 @@ hipError_t launch_read_message(const uint8_t* in, const uint64_t* in_off, const 
 hipError_t launch_copy_jobs(const uint64_t* jobs, uint32_t nj, hipStream_t stream);
 hipError_t launch_read_header(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                               uint64_t* out_len, uint64_t* consumed, int32_t* status, hipStream_t stream);
-// Framer walk (capnp_packed_framer_read): spec_q (framer_spec_bytes(nl, windows) bytes, u64 at
-// u32 index 8 = windows) holds the window tables of the listed connections whose held bytes
+// Framer walk (capnp_packed_framer_read): spec_q (framer_spec_bytes(nl, windows) bytes, the u64
+// at u32 index kSlotReserved of class_ws.h = windows) holds the window tables of the listed connections whose held bytes
 // span more than one window (spec_first / spec_count per list entry, spec_off / spec_len their
 // bytes from the walk's start); spec_q null or windows 0: every window walked exactly.
 size_t framer_spec_bytes(uint32_t nl, uint64_t windows);

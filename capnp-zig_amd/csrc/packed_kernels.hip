@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "capnp_packed.h"
+#include "class_ws.h"
 #include "kernels.h"
 
 namespace cpk {
@@ -946,18 +947,8 @@ __device__ __forceinline__ bool encode_tiled_unit(const uint8_t* in, uint64_t of
            (len >> 3) <= 0xFFFFF000ull;
 }
 
-// Long-unit lists (device memory, filled by the class kernels below) for a batch of n
-// units: q[0] = long units listed, q[2] = huge units listed (more than kQHuge bytes in);
-// the long units at q[kQHead ..] upwards, the huge ones from q[kQHead + n - 1] downwards.
-// long_tiles_kernel / long_windows_kernel turn them into the tile / window tables (huge
-// units first) and the serial list of units the table could not hold.
-constexpr uint64_t kQHuge = 65536;
-constexpr uint32_t kQHead = 32;
-constexpr uint32_t kClassBlock = 1024;  // units per class-kernel block
-constexpr uint32_t kClassK = 12;        // per-block class counters (11 classes used)
-__host__ __device__ inline uint64_t class_blocks(uint64_t n) { return (n + kClassBlock - 1) / kClassBlock; }
-// u32 index of the serial list (long units no tile / window table could hold)
-__host__ __device__ inline uint64_t serial_off(uint64_t n) { return kQHead + 3 * n + kClassK * class_blocks(n); }
+// The class workspace q (lists, counters, tile / window table): class_ws.h.
+constexpr uint64_t kQHuge = 65536;  // long units of more bytes in than this are huge
 // Units longer than one tile (encode_tiled_unit) that the tile table could not hold,
 // taken from the serial list and encoded one after another, tile by tile.
 template <bool WRITE>
@@ -973,7 +964,7 @@ __global__ __launch_bounds__(kBlock) void encode_tiled_kernel(const uint8_t* __r
     __shared__ __attribute__((aligned(16))) uint64_t lut[256];
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (q[5] == 0) return;  // no serial units (block-uniform)
+    if (q[kSlotSerial] == 0) return;  // no serial units (block-uniform)
     if (WRITE) {
         lut[threadIdx.x] = compact_selector(threadIdx.x);
         __syncthreads();
@@ -985,9 +976,9 @@ __global__ __launch_bounds__(kBlock) void encode_tiled_kernel(const uint8_t* __r
     for (;;) {  // wave-uniform
     {
         uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(q + 10, 1u);
+        if (lane == 0) i = atomicAdd(q + kSlotSerialTake, 1u);
         i = __builtin_amdgcn_readfirstlane(i);
-        if (i >= q[5]) break;
+        if (i >= q[kSlotSerial]) break;
         unit = serial[i];
     }
     const uint8_t* const src = in + in_off[unit];
@@ -2900,7 +2891,7 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
     constexpr bool CK = SEL == kWvMarked;
     if (CK && q && *q == 0) return;  // kWvMarked with a count of marked units: none
     const bool QD = SEL == kWvLong;
-    if (QD && q[5] == 0) return;  // no serial units (block-uniform)
+    if (QD && q[kSlotSerial] == 0) return;  // no serial units (block-uniform)
     lut[threadIdx.x] = expand_selector(threadIdx.x);
     __syncthreads();
     const uint32_t lane = lane_id();
@@ -2911,7 +2902,7 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
     // small grid striding over the batch (64 statuses per load). QD: the serial list, a
     // wave per entry striding over it (no shared atomic cursor: contended takes serialise).
     const uint32_t* const serial = q + serial_off(n);
-    const uint32_t nq = QD ? q[5] : n;
+    const uint32_t nq = QD ? q[kSlotSerial] : n;
     const uint32_t stride = QD ? gridDim.x * kWvWaves : gridDim.x * kWvWaves * kWave;
     for (uint32_t ubase = QD ? blockIdx.x * kWvWaves + wave : (blockIdx.x * kWvWaves + wave) * kWave; ubase < nq;
          ubase += stride) {
@@ -3017,7 +3008,7 @@ constexpr uint32_t kFlPieces = 320;               // pass-2 window: 64 lanes x 5
 constexpr uint64_t kIxSizeMax = 1ull << 31;       // size-only walk: longer units use decode_size_lane_kernel
 // record bytes per unit: 64 B per 8 rounds (+1 store) of at most kFlPieces * 16 B
 constexpr uint32_t kRecStride = 64 * ((kFlPieces * 16 / 64 + 8) / 8);
-static_assert(kRecStride == 704, "record region stride");
+static_assert(kRecStride == kRecBytes, "record region stride (class_ws.h)");
 
 // The units the indexed decoder's fallback owns (the long-unit decoders): an 8-aligned
 // output slot and a packed length pass 2 cannot stage (> kFlPieces pieces). Passes 1
@@ -3998,17 +3989,13 @@ __global__ __launch_bounds__(kLwWaves * kWave) void decode_words_kernel(
 //          decode_fill_kernel, a wave per unit);
 //   long, huge: a wave per unit walking it tile by tile / window by window
 //          (encode_tiled_kernel / decode_wave_kernel<kWvLong>), on the side stream.
-// Workspace q (queue_bytes(n)): q[0] long, q[2] huge, q[3] small and q[4] mid counts, q[5]
-// serial units, q[8..9] tiles / windows listed, q[10] serial take cursor, q[11 + b] mid units before bin b; the long list at q[kQHead ..] upwards and the huge list from
-// q[kQHead + n - 1] downwards, the small list at q[kQHead + n ..], the mid list at
-// q[kQHead + 2n ..], kClassK counts per class block, the serial list (serial_off), then the
-// tile table (encode) or the window table (decode). Count, scan, scatter: each list keeps
-// batch order, and no atomic is contended.
+// The workspace q (queue_bytes(n)) the lists and their counters live in: class_ws.h. Count, scan,
+// scatter: each list keeps batch order, and no atomic is contended.
 // decode mid units are binned by packed length (CL_MID + 0..7: <= 768, 1024, 1280, 1536, 2048,
 // 2560, 3072, more bytes), so the lanes of an index-pass or words-decoder wave walk units of
 // similar length in lockstep; the mid list is the bins in order (batch order within a bin), and
-// q[20] is the two-pass decoder's share of it (class_scan_kernel).
-enum : uint32_t { CL_LONG = 0, CL_HUGE = 1, CL_SMALL = 2, CL_MID = 3, CL_MID_BINS = 8 };
+// its front is the two-pass decoder's share (kSlotTwoPass, class_scan_kernel).
+enum : uint32_t { CL_LONG = 0, CL_HUGE = 1, CL_SMALL = 2, CL_MID = 3 };  // + bins 0 .. CL_MID_BINS - 1
 constexpr uint32_t kEsBinsQ = 4;  // encode's small-unit bins (mid-list bins 4 .. 7, kEsBins)
 constexpr uint64_t kSmEncWords = 64;  // encode: units of at most 64 words are small
 constexpr uint64_t kSmDecP = 512;     // decode: small = at most 512 packed bytes ...
@@ -4016,7 +4003,7 @@ constexpr uint64_t kSmDecCap = 8192;  // ... into a slot of at most 8 KiB
 constexpr uint64_t kMidSplitP = 1280; // decode: mid units of at most this many packed bytes (bins 0 .. 2)
 constexpr uint64_t kWordsCapMax = 8192;  // decode: the words decoder takes slots of at most 8 KiB
 
-__device__ __forceinline__ uint32_t* q_blocks(uint32_t* q, uint32_t n) { return q + kQHead + 3ull * n; }
+__device__ __forceinline__ uint32_t* q_blocks(uint32_t* q, uint32_t n) { return q + block_counts_off(n); }
 
 // KIND 1: decode (small lane kernel + words / indexed mid decoders), 2: decoded size (no output:
 // long by packed length alone), 4: encode with the streaming small-unit encoder (mid units bin
@@ -4111,23 +4098,23 @@ __global__ __launch_bounds__(1024) void class_scan_kernel(uint32_t* q, uint32_t 
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        q[0] = carry[CL_LONG];
-        q[2] = carry[CL_HUGE];
-        q[3] = carry[CL_SMALL];
-        uint32_t mid = 0;  // q[11 + b]: mid units in the bins before bin b
+        q[kSlotLong] = carry[CL_LONG];
+        q[kSlotHuge] = carry[CL_HUGE];
+        q[kSlotSmall] = carry[CL_SMALL];
+        uint32_t mid = 0;  // the mid units in the bins before bin b
         for (uint32_t b = 0; b < CL_MID_BINS; ++b) {
-            q[11 + b] = mid;
+            q[kSlotMidBefore + b] = mid;
             mid += carry[CL_MID + b];
         }
-        q[4] = mid;
-        // decode: the mid list's share for the two-pass decoder, [0, q[20]); the words decoder
-        // takes [q[20], mid). words_min 0: all to the words decoder; else the units over
+        q[kSlotMid] = mid;
+        // decode: the mid list's share for the two-pass decoder, [0, two_pass); the words decoder
+        // takes [two_pass, mid). words_min 0: all to the words decoder; else the units over
         // kMidSplitP packed bytes (bins 3 .. 7) when there are at least words_min of them
         // (the words decoder is a throughput design, and a wave's walk of
         // ~600 steps is long: under a resident grid of units, or at p ~ 0.9, two-pass wins)
-        const uint32_t over = mid - q[11 + 3];
-        q[20] = words_min == 0 ? 0u : (over >= words_min ? q[11 + 3] : mid);
-        q[21] = 0;  // decode_words_kernel's count of units stopped at their slot's capacity
+        const uint32_t over = mid - q[kSlotMidBefore + 3];
+        q[kSlotTwoPass] = words_min == 0 ? 0u : (over >= words_min ? q[kSlotMidBefore + 3] : mid);
+        q[kSlotCapped] = 0;  // decode_words_kernel's count of units stopped at their slot's capacity
     }
 }
 
@@ -4189,7 +4176,7 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
             pre_s[threadIdx.x] += b;
         }
         __syncthreads();
-        if (threadIdx.x == 0) {  // q[11 + b]: mid units in the bins before bin b (class_scan_kernel)
+        if (threadIdx.x == 0) {  // the mid units in the bins before bin b (class_scan_kernel)
             uint32_t mid = 0;
             for (uint32_t b = 0; b < CL_MID_BINS; ++b) {
                 midb_s[b] = mid;
@@ -4201,12 +4188,12 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
         if (blockIdx.x == 0 && threadIdx.x < kQHead) {  // the head, as class_scan_kernel writes it
             const uint32_t t = threadIdx.x, mid = midb_s[CL_MID_BINS];
             uint32_t v = 0;
-            if (t == 0) v = tot_s[CL_LONG];
-            else if (t == 2) v = tot_s[CL_HUGE];
-            else if (t == 3) v = tot_s[CL_SMALL];
-            else if (t == 4) v = mid;
-            else if (t >= 11 && t < 11 + CL_MID_BINS) v = midb_s[t - 11];
-            else if (t == 20) v = words_min == 0 ? 0u : (mid - midb_s[3] >= words_min ? midb_s[3] : mid);
+            if (t == kSlotLong) v = tot_s[CL_LONG];
+            else if (t == kSlotHuge) v = tot_s[CL_HUGE];
+            else if (t == kSlotSmall) v = tot_s[CL_SMALL];
+            else if (t == kSlotMid) v = mid;
+            else if (t >= kSlotMidBefore && t < kSlotMidBefore + CL_MID_BINS) v = midb_s[t - kSlotMidBefore];
+            else if (t == kSlotTwoPass) v = words_min == 0 ? 0u : (mid - midb_s[3] >= words_min ? midb_s[3] : mid);
             q[t] = v;
         }
     }
@@ -4227,21 +4214,21 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
                 pb = pre_s[cc];
                 pn = pb + own_s[cc];
             } else {
-                const uint32_t tot = (b + 1 < CL_MID_BINS ? q[12 + b] : q[4]) - q[11 + b];
+                const uint32_t tot = q[mid_through_slot(b)] - q[kSlotMidBefore + b];
                 pb = P[blockIdx.x * kClassK + cc];
                 pn = blockIdx.x + 1 < nb ? P[(blockIdx.x + 1) * kClassK + cc] : tot;
             }
             before += pb + (cc < c ? pn - pb : 0u);
         }
         idx = before + (idx - pc);
-        const uint32_t base = fused ? midb_s[CL_MID_BINS - kEsBinsQ] : q[11 + CL_MID_BINS - kEsBinsQ];
-        q[kQHead + 2ull * n + base + idx] = u;
+        const uint32_t base = fused ? midb_s[CL_MID_BINS - kEsBinsQ] : q[kSlotMidBefore + CL_MID_BINS - kEsBinsQ];
+        q[mid_list_off(n) + base + idx] = u;
         return;
     }
-    if (c == CL_LONG) q[kQHead + idx] = u;
-    else if (c == CL_HUGE) q[kQHead + n - 1 - idx] = u;
-    else if (c == CL_SMALL) q[kQHead + 1ull * n + idx] = u;
-    else q[kQHead + 2ull * n + (fused ? midb_s[c - CL_MID] : q[11 + (c - CL_MID)]) + idx] = u;
+    if (c == CL_LONG) q[long_slot(idx)] = u;
+    else if (c == CL_HUGE) q[huge_slot(n, idx)] = u;
+    else if (c == CL_SMALL) q[small_list_off(n) + idx] = u;
+    else q[mid_list_off(n) + (fused ? midb_s[c - CL_MID] : q[kSlotMidBefore + (c - CL_MID)]) + idx] = u;
 }
 
 // ---- ENCODE, long units, tile-parallel --------------------------------
@@ -4257,9 +4244,8 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
 //   tile_encode_kernel<kTilesWrite>  per tile: its output offset = the unit's earlier
 //                      tiles' sizes (one wave reduction), the tile coded again and
 //                      written there; the unit's last tile writes out_len and status.
-// The table lives in the class workspace after the class lists: tile sizes (u64), units,
-// first tile of the unit; capacity n + kTileExtra tiles.
-constexpr uint64_t kTileExtra = 65536;
+// The table lives in the class workspace after the class lists (class_ws.h): tile sizes
+// (u64), units, first tile of the unit; capacity tile_cap(n) tiles.
 constexpr uint32_t kTileSkip = 0xFFFFFFFFu;  // a table entry of a unit that went to the serial list
 struct TileTab {
     uint64_t* size;
@@ -4268,20 +4254,23 @@ struct TileTab {
     uint32_t* serial;
     uint64_t cap;
 };
-__host__ __device__ inline uint64_t tile_tab_off(uint64_t n) {  // u32 index of the tile table (8-B aligned)
-    return (serial_off(n) + n + 1) & ~1ull;
-}
+static_assert(sizeof(*TileTab::size) + sizeof(*TileTab::unit) + sizeof(*TileTab::first) == kTileEntBytes,
+              "tile table entry");
 __device__ __forceinline__ TileTab tile_tab(uint32_t* q, uint32_t n) {
     TileTab t;
-    t.cap = (uint64_t)n + kTileExtra;
+    t.cap = tile_cap(n);
     t.serial = q + serial_off(n);
     t.size = reinterpret_cast<uint64_t*>(q + tile_tab_off(n));
-    t.unit = q + tile_tab_off(n) + 2 * t.cap;
+    // = q + tile_unit_off(n), q + tile_first_off(n); summed column by column from the table's
+    // start, which the tile kernels' generated code depends on (make asm-digest)
+    t.unit = q + tile_tab_off(n) + tile_unit_col(t.cap);
     t.first = t.unit + t.cap;
     return t;
 }
-// q[5]: serial units; q[8..9]: tiles reserved (u64); q[10]: serial take cursor
-__device__ __forceinline__ unsigned long long* q_tiles(uint32_t* q) { return reinterpret_cast<unsigned long long*>(q + 8); }
+// tiles / windows reserved so far (u64)
+__device__ __forceinline__ unsigned long long* q_tiles(uint32_t* q) {
+    return reinterpret_cast<unsigned long long*>(q + kSlotReserved);
+}
 
 // Consecutive ranges of a shared counter for a wave's lanes (k each, 0: none), in lane order,
 // with ONE atomic per wave: ~10K long units each adding to the one counter serialised at its L2
@@ -4302,13 +4291,13 @@ __device__ __forceinline__ uint64_t wave_reserve(unsigned long long* ctr, uint64
 }
 
 __global__ __launch_bounds__(256) void long_tiles_kernel(const uint64_t* __restrict__ in_len, uint32_t n, uint32_t* q) {
-    const uint32_t nh = q[2], nl = q[0];
+    const uint32_t nh = q[kSlotHuge], nl = q[kSlotLong];
     const TileTab t = tile_tab(q, n);
     // as long_windows_kernel: wave-uniform trips, one reservation per wave
     for (uint32_t i0 = blockIdx.x * 256 + (threadIdx.x & ~(kWave - 1)); i0 < nl + nh; i0 += gridDim.x * 256) {
     const uint32_t i = i0 + lane_id();
     const bool v = i < nl + nh;
-    const uint32_t unit = !v ? 0u : (i < nh ? q[kQHead + n - 1 - i] : q[kQHead + (i - nh)]);
+    const uint32_t unit = !v ? 0u : q[long_list_slot(n, nh, i)];
     const uint64_t k = v ? ((in_len[unit] >> 3) + kEncMaxWords - 1) / kEncMaxWords : 0ull;  // >= 2 tiles
     const uint64_t r = wave_reserve(q_tiles(q), (v && k <= t.cap) ? k : 0ull);
     if (!v) continue;
@@ -4320,7 +4309,7 @@ __global__ __launch_bounds__(256) void long_tiles_kernel(const uint64_t* __restr
         }
     } else {
         for (uint64_t j = base; j < t.cap; ++j) t.unit[j] = kTileSkip;  // reserved past the end: unused
-        t.serial[atomicAdd(q + 5, 1u)] = unit;
+        t.serial[atomicAdd(q + kSlotSerial, 1u)] = unit;
     }
     }
 }
@@ -4468,9 +4457,8 @@ __global__ __launch_bounds__(kBlock) void tile_encode_kernel(const uint8_t* __re
 //                         writes nothing (message.zig:90 errors before producing output);
 //   window_fill_kernel    per window of an OK unit: the chain from its exact entry, the
 //                         code list and the expansion (wv_expand) at its output offset.
-// The table shares the class workspace's tile-table region (encode's); capacity
-// n / 8 + kWinExtra windows (4.6 KB each).
-constexpr uint64_t kWinExtra = 32768;
+// The table shares the class workspace's tile-table region (encode's; class_ws.h); capacity
+// win_cap(n) windows (4.6 KB each).
 constexpr uint32_t kWinNone = 0xFFFFFFFFu;  // window entry: nothing to expand
 constexpr int16_t kDeltaEof = -32768;       // delta: the chain from this entry runs past the unit's end
 constexpr uint32_t kWinD = 64;              // entries the spec pass resolves (window bytes 0 .. 63)
@@ -4484,16 +4472,14 @@ struct WinEnt {
     uint64_t pad2;
     int16_t delta[kWinD];  // spec pass: words from entry d - total (kDeltaEof: truncated)
 };
-static_assert(sizeof(WinEnt) == 176, "window table entry");
-__host__ __device__ inline uint64_t win_tab_off(uint64_t n) { return (tile_tab_off(n) + 3) & ~3ull; }  // 16-B aligned
-__host__ __device__ inline uint64_t win_cap(uint64_t n) { return n / 8 + kWinExtra; }
+static_assert(sizeof(WinEnt) == kWinEntBytes, "window table entry");
 __device__ __forceinline__ WinEnt* win_tab(uint32_t* q, uint32_t n) {
     return reinterpret_cast<WinEnt*>(q + win_tab_off(n));
 }
 
 __global__ __launch_bounds__(256) void long_windows_kernel(const uint64_t* __restrict__ in_len, uint32_t n,
                                                            uint32_t* q) {
-    const uint32_t nh = q[2], nl = q[0];
+    const uint32_t nh = q[kSlotHuge], nl = q[kSlotLong];
     WinEnt* const e = win_tab(q, n);
     const uint64_t cap = win_cap(n);
     // a small grid (list_blocks) striding over the long list, wave-uniform trips; the windows
@@ -4501,7 +4487,7 @@ __global__ __launch_bounds__(256) void long_windows_kernel(const uint64_t* __res
     for (uint32_t i0 = blockIdx.x * 256 + (threadIdx.x & ~(kWave - 1)); i0 < nl + nh; i0 += gridDim.x * 256) {
     const uint32_t i = i0 + lane_id();
     const bool v = i < nl + nh;
-    const uint64_t slot = !v ? 0ull : (i < nh ? kQHead + n - 1 - i : kQHead + (i - nh));
+    const uint64_t slot = !v ? 0ull : long_list_slot(n, nh, i);
     const uint32_t unit = v ? q[slot] : 0u;
     const uint64_t k = v ? (in_len[unit] + kWvWin - 1) / kWvWin : 0ull;  // >= 1 (P > 0)
     const uint64_t r = wave_reserve(q_tiles(q), (v && k <= cap) ? k : 0ull);
@@ -4515,7 +4501,7 @@ __global__ __launch_bounds__(256) void long_windows_kernel(const uint64_t* __res
         q[slot] = (uint32_t)base;  // the list entry now names the unit's first window (resolve pass)
     } else {
         for (uint64_t j = base; j < cap; ++j) e[j].unit = kTileSkip;  // reserved past the end: unused
-        q[serial_off(n) + atomicAdd(q + 5, 1u)] = unit;  // the serial list
+        q[serial_off(n) + atomicAdd(q + kSlotSerial, 1u)] = unit;  // the serial list
         q[slot] = kTileSkip;
     }
     }
@@ -4617,7 +4603,7 @@ __global__ __launch_bounds__(kWvBlock) void window_resolve_kernel(const uint8_t*
     __shared__ __attribute__((aligned(16))) uint8_t pk_all[kWvWaves * kWvPk];
     __shared__ __attribute__((aligned(16))) uint8_t mk_all[kWvWaves * kWvWin];
     __shared__ int16_t dl_all[kWvWaves][kWinBatch][kWinD];
-    const uint32_t nlist = q[0] + q[2];
+    const uint32_t nlist = q[kSlotLong] + q[kSlotHuge];
     if ((uint64_t)blockIdx.x * kWvWaves >= nlist) return;  // block-uniform
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -4628,8 +4614,7 @@ __global__ __launch_bounds__(kWvBlock) void window_resolve_kernel(const uint8_t*
     // a wave per listed long unit: the list entry names its first window (long_windows_kernel)
     for (uint32_t li = blockIdx.x * kWvWaves + wave; li < nlist; li += G) {
         {
-            const uint32_t nh = q[2];
-            const uint32_t b0 = q[li < nh ? kQHead + n - 1 - li : kQHead + (li - nh)];
+            const uint32_t b0 = q[long_list_slot(n, q[kSlotHuge], li)];
             if (b0 == kTileSkip) continue;  // the serial decoder's
             const uint64_t g0 = b0;
             const uint32_t unit = __builtin_amdgcn_readfirstlane(tab[g0].unit);
@@ -4783,9 +4768,9 @@ __global__ __launch_bounds__(kEsWaves * kWave) void encode_stream_kernel(
     uint8_t* const ring_all = ring_blk + wave * (kWave * kEsRing);
     const uint32_t lane = lane_id();
     // the small units: mid-list bins 4 .. 7 (unit_class<4>)
-    const uint32_t b0i = q[11 + CL_MID_BINS - kEsBins];
-    const uint32_t count = q[4] - b0i;
-    const uint32_t* const list = q + kQHead + 2ull * n + b0i;
+    const uint32_t b0i = q[kSlotMidBefore + CL_MID_BINS - kEsBins];
+    const uint32_t count = q[kSlotMid] - b0i;
+    const uint32_t* const list = q + mid_list_off(n) + b0i;
     const uint32_t wv = blockIdx.x * kEsWaves + wave;
     if (wv * kWave >= count) return;  // wave-uniform
     const uint32_t slot = wv * kWave + lane;
@@ -5009,8 +4994,8 @@ __global__ __launch_bounds__(kSmBlock) void decode_small_kernel(const uint8_t* _
     const uint32_t wbase_t = threadIdx.x & ~(kWave - 1);
     lut[threadIdx.x] = expand_selector(threadIdx.x);
     __syncthreads();
-    const uint32_t count = q[3];
-    const uint32_t* const list = q + kQHead + n;
+    const uint32_t count = q[kSlotSmall];
+    const uint32_t* const list = q + small_list_off(n);
     const uint32_t lane = lane_id();
     const uint32_t gw = blockIdx.x * (kSmBlock / kWave) + (threadIdx.x >> 6);
     const uint32_t GW = gridDim.x * (kSmBlock / kWave);
@@ -5306,8 +5291,8 @@ __global__ __launch_bounds__(kSgWaves * kWave) void decode_small_group_kernel(
     __shared__ uint32_t pfx_all[kSgWaves][2][kWave];  // exclusive prefix: pieces, output pairs
     for (uint32_t i = threadIdx.x; i < 256; i += kSgWaves * kWave) lut[i] = expand_selector(i);
     __syncthreads();
-    const uint32_t count = q[3];
-    const uint32_t* const list = q + kQHead + n;
+    const uint32_t count = q[kSlotSmall];
+    const uint32_t* const list = q + small_list_off(n);
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t* const pin = pin_all[wave];
@@ -6319,7 +6304,7 @@ struct StreamCtx {
     hipEvent_t fork = nullptr, join = nullptr;
     hipStream_t s2 = nullptr;  // a second side stream (CAPNP_PACKED_LAUNCH_MID_SIDE_STREAM: C5's mid units)
     hipEvent_t join2 = nullptr;
-    uint32_t* q = nullptr;  // class workspace (queue_bytes): kQHead counters, lists, tile / window table
+    uint32_t* q = nullptr;  // class workspace (queue_bytes; class_ws.h)
     uint64_t qcap = 0;
     bool q_captured = false;         // q was used inside a hipGraph capture
     std::vector<uint32_t*> retired;  // replaced queues a capture used (graphs may reference them)
@@ -6338,16 +6323,7 @@ static std::mutex g_ctx_mu;
 // drops it from the map meanwhile (no use-after-free, whatever the callers do).
 static std::map<std::pair<int, uintptr_t>, std::shared_ptr<StreamCtx>> g_ctx;
 
-// Byte offset of the piece-record region (decode: kRecStride per mid-list entry) in the
-// class workspace, after the lists and the tile / window table.
-static uint64_t rec_region_off(uint32_t n) {
-    // lists, serial list, then the tile table (encode) or the window table (decode)
-    const uint64_t tiles = tile_tab_off(n) * sizeof(uint32_t) + 16 * ((uint64_t)n + kTileExtra);
-    const uint64_t wins = win_tab_off(n) * sizeof(uint32_t) + sizeof(WinEnt) * win_cap(n);
-    return ((tiles > wins ? tiles : wins) + 255) & ~255ull;
-}
-
-size_t queue_bytes(uint32_t n) { return rec_region_off(n) + (uint64_t)kRecStride * n; }
+size_t queue_bytes(uint32_t n) { return class_ws_bytes(n); }
 
 // Resident blocks of a kernel across the device (hipOccupancy...), for persistent grids.
 template <typename K>
@@ -6585,12 +6561,13 @@ hipError_t launch_encode(const uint8_t* in, const uint64_t* in_off, const uint64
     uint32_t* const q = side.queue(n);
     if (!q) return ws ? hipErrorInvalidValue : hipErrorOutOfMemory;
     launch_classes<4>(in, in_off, in_len, n, out, out_off, out_cap, q, status, stream);
-    const uint32_t* const mid_count = q + 12;  // bin 0: the units before bin 1
+    const ClassWs cw{q, n};
+    const uint32_t* const mid_count = cw.slot(mid_through_slot(0));  // bin 0: the units before bin 1
     const uint32_t es_blocks = (n + kEsWaves * kWave - 1) / (kEsWaves * kWave);  // waves past the count exit
     hipError_t e = side.fork();
     if (e != hipSuccess) return e;
     const hipStream_t ss = side.stream();
-    const uint32_t* const mid = q + kQHead + 2ull * n;
+    const uint32_t* const mid = cw.mid();
     static const uint32_t tiles_res = resident_blocks(tile_encode_kernel<kTilesWrite, true>, kBlock, 4);
     // mid units on a second side stream beside the small-unit kernel (LAUNCH_MID_SIDE_STREAM)
     const hipStream_t ms = mid_side_stream() ? side.stream2() : stream;
@@ -6661,6 +6638,7 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
         uint32_t* const q = side.queue(n);
         if (!q) return ws ? hipErrorInvalidValue : hipErrorOutOfMemory;
         launch_classes<2>(in, in_off, in_len, n, nullptr, nullptr, nullptr, q, status, stream);
+        const ClassWs cw{q, n};
         hipError_t e = side.fork();
         if (e != hipSuccess) return e;
         static const uint32_t spec_res = resident_blocks(window_spec_kernel, kWvBlock, 4);
@@ -6673,10 +6651,11 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
         window_spec_kernel<<<win_blocks, kWvBlock, 0, ss>>>(in, in_off, in_len, n, q);
         window_resolve_kernel<<<res_blocks, kWvBlock, 0, ss>>>(in, in_off, in_len, n, nullptr, out_len, status, q);
         decode_index_kernel<true><<<ix_blocks_for(n), kWave * kIxBw, 0, ss>>>(in, in_off, in_len, n, nullptr, nullptr, nullptr,
-                                                               out_len, status, nullptr, q + serial_off(n), q + 5);
+                                                               out_len, status, nullptr, cw.serial(),
+                                                               cw.slot(kSlotSerial));
         decode_index_kernel<true><<<ix_blocks_for(n), kWave * kIxBw, 0, stream>>>(in, in_off, in_len, n, nullptr, nullptr, nullptr,
-                                                                   out_len, status, nullptr, q + kQHead + 2ull * n,
-                                                                   q + 4);
+                                                                   out_len, status, nullptr, cw.mid(),
+                                                                   cw.slot(kSlotMid));
         e = hipGetLastError();
         const hipError_t j = side.join();
         if (e == hipSuccess) e = j;
@@ -6722,7 +6701,10 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
     window_fill_kernel<<<wfill_blocks, kWvBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, status, q);
     decode_wave_kernel<kWvLong><<<long_blocks, kWvBlock, 0, ss>>>(in, in_off, in_len, n, out, out_off, out_cap,
                                                                    out_len, status, q);
-    const uint32_t* const mid = q + kQHead + 2ull * n;
+    const ClassWs cw{q, n};
+    const uint32_t* const mid = cw.mid();
+    uint8_t* const rec = cw.rec();  // piece records, off the output slots
+    uint32_t* const n_mid = cw.slot(kSlotMid);
     // the small units' kernel: on the caller's stream, before the mid units' passes or, when those
     // go on a second side stream (mid_side_stream), after their launches
     const auto launch_small = [&] {
@@ -6741,26 +6723,26 @@ hipError_t launch_decode(const uint8_t* in, const uint64_t* in_off, const uint64
     if (!mid_stream) launch_small();
     // mid units: the indexed two-pass decoder (index pass + fill pass) and, where it pays, the
     // single-read words decoder (capnp_packed_set_decoder)
-    if (words) {  // [0, q[20]) two-pass, [q[20], q[4]) words (either may be empty)
+    if (words) {  // [0, two_pass) two-pass, [two_pass, mid count) words (either may be empty)
         const uint32_t lw_blocks = (n + kLwWaves * kWave - 1) / (kLwWaves * kWave);
-        uint8_t* const rec = reinterpret_cast<uint8_t*>(q) + rec_region_off(n);
+        uint32_t* const two_pass = cw.slot(kSlotTwoPass);
+        uint32_t* const capped = cw.slot(kSlotCapped);
         decode_index_kernel<false><<<ix_blocks_for(n), kWave * kIxBw, 0, ms>>>(
-            in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mid, q + 20, rec);
+            in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mid, two_pass, rec);
         decode_fill_kernel<<<fill_blocks(n), kFlWaves * kWave, 0, ms>>>(in, in_off, in_len, n, out, out_off,
-                                                                           out_len, out_cap, status, mid, q + 20, rec);
+                                                                           out_len, out_cap, status, mid, two_pass, rec);
         decode_words_kernel<false><<<lw_blocks, kLwWaves * kWave, 0, ms>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                          out_len, status, mid, q + 4, q + 20, q + 21,
+                                                                          out_len, status, mid, n_mid, two_pass, capped,
                                                                           nullptr);
-        // the words decoder's units stopped at their slot's capacity with input left (q[21] of them,
-        // usually none: the kernel returns at once)
+        // the words decoder's units stopped at their slot's capacity with input left (usually none:
+        // the kernel returns at once)
         decode_wave_kernel<kWvMarked><<<fallback_blocks(n), kWvBlock, 0, ms>>>(in, in_off, in_len, n, out, out_off,
-                                                                            out_cap, out_len, status, q + 21);
+                                                                            out_cap, out_len, status, capped);
     } else {
-        uint8_t* const rec = reinterpret_cast<uint8_t*>(q) + rec_region_off(n);  // piece records, off the output slots
         decode_index_kernel<false><<<ix_blocks_for(n), kWave * kIxBw, 0, ms>>>(
-            in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mid, q + 4, rec);
+            in, in_off, in_len, n, out, out_off, out_cap, out_len, status, nullptr, mid, n_mid, rec);
         decode_fill_kernel<<<fill_blocks(n), kFlWaves * kWave, 0, ms>>>(in, in_off, in_len, n, out, out_off,
-                                                                           out_len, out_cap, status, mid, q + 4, rec);
+                                                                           out_len, out_cap, status, mid, n_mid, rec);
     }
     if (mid_stream) launch_small();
     e = hipGetLastError();
@@ -6937,7 +6919,7 @@ __global__ __launch_bounds__(256) void framer_windows_kernel(const uint32_t* __r
         }
 }
 
-size_t framer_spec_bytes(uint32_t nl, uint64_t windows) { return 4 * win_tab_off(nl) + sizeof(WinEnt) * windows; }
+size_t framer_spec_bytes(uint32_t nl, uint64_t windows) { return framer_spec_ws_bytes(nl, windows); }
 uint32_t framer_window_bytes() { return kWvWin; }
 uint64_t framer_window_cap(uint32_t nl) { return win_cap(nl); }
 

@@ -208,6 +208,41 @@ def test_misaligned_workspace_is_rejected():
     b.check_roundtrip()
 
 
+def test_exact_workspace_between_sentinels():
+    """A caller workspace of exactly capnp_packed_batch_workspace_bytes(n) bytes, cut from a larger
+    buffer with 256 sentinel bytes on either side: encode, decode and decoded-size of a batch
+    with units of every class (two class blocks) leave both sentinels as they were. The ABI has
+    no decoded-size call with a caller workspace; that call runs on the library's own."""
+    n = 1100
+    sizes = mixed_sizes(n, 13)
+    assert (sizes <= 512).any() and (sizes > 65536).any()  # small and huge units
+    assert ((sizes > 4096) & (sizes <= 65536)).sum() >= 3  # long units
+    b = Batch(sizes, seed=0xC0DE0441)
+    wb = cp.lib().capnp_packed_batch_workspace_bytes(n)
+    buf = torch.full((wb + 1024,), 0xA5, dtype=torch.uint8, device=DEV)
+    lo = 256 + (-(buf.data_ptr() + 256)) % 256  # 256-B aligned, at least 256 B in
+    ws = buf[lo:lo + wb]
+    assert ws.data_ptr() % 256 == 0 and ws.numel() == wb and lo + wb + 256 <= buf.numel()
+
+    def sentinels_intact():
+        torch.cuda.synchronize()
+        return (buf[:lo] == 0xA5).all().item() and (buf[lo + wb:] == 0xA5).all().item()
+
+    cp.encode_batch(b.d_in, b.in_off, b.sizes, b.d_pk, b.pk_off, b.cap, b.plen, b.pst, ws=ws)
+    assert sentinels_intact(), "encode wrote outside its workspace"
+    plen = b.plen.cpu().numpy()
+    mid = plen[(plen > 512) & (sizes <= 4096)]  # decode's mid units, binned by packed length
+    assert len(set(np.searchsorted([768, 1024, 1280, 1536, 2048, 2560, 3072], mid, side="left"))) >= 3
+    cp.decode_batch(b.d_pk, b.pk_off, b.plen, b.d_out, b.in_off, b.sizes, b.ulen, b.ust, ws=ws)
+    assert sentinels_intact(), "decode wrote outside its workspace"
+    b.check_roundtrip()
+    dlen = torch.zeros_like(b.ulen)
+    dst = torch.full_like(b.ust, -1)
+    cp.decoded_size_batch(b.d_pk, b.pk_off, b.plen, dlen, dst)
+    assert sentinels_intact(), "decoded-size wrote outside its workspace"
+    assert (dst == 0).all().item() and torch.equal(dlen, b.sizes)
+
+
 def test_queue_growth_is_bounded_and_released():
     """Growing batches on one stream: the library's queue grows geometrically, replaced
     queues are freed (none was captured), device memory stays bounded, and
