@@ -325,8 +325,11 @@ int capnp_packed_read_message(const uint8_t* in, size_t n, uint8_t* out, size_t 
  * from index d_seg_first[i] of d_seg_ptr (device addresses, 8-byte aligned) and
  * d_seg_len (bytes, multiples of 8, as a MessageBuilder's segments are). At most
  * 512 segments per message (Message.max_segment_count, message.zig:310): more,
- * or a misaligned segment, gives INVALID_ARGUMENT. Output as in
- * capnp_packed_encode_batch; d_out == NULL computes the packed sizes only. */
+ * or a misaligned segment, gives INVALID_ARGUMENT (d_out_len 0, the slot untouched). Output
+ * as in capnp_packed_encode_batch; d_out == NULL computes the packed sizes only. An empty
+ * segment's address is checked for alignment and never read; with d_seg_count[i] == 0,
+ * d_seg_first[i] is not used. Every d_status and d_out_len entry is written, whatever the
+ * arrays held before the call. */
 int capnp_packed_encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len,
                                       const uint32_t* d_seg_first, const uint32_t* d_seg_count, uint32_t n,
                                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
@@ -425,7 +428,12 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
  * d_in[d_in_off[i] + d_seg_off[i*max_segs + j] .. + d_seg_len[i*max_segs + j]).
  * Errors per message: END_OF_STREAM (< 4 bytes), INVALID_SEGMENT_COUNT,
  * SEGMENT_COUNT_LIMIT_EXCEEDED, TRUNCATED_MESSAGE. Trailing bytes after the last
- * segment are ignored, as in the reference. */
+ * segment are ignored, as in the reference. d_in_off may be any byte value.
+ * Rows: an OK message's entries j >= min(count, max_segs) are not written (segments past
+ * max_segs are counted, not listed). A failed message gets d_seg_count 0; its row's content is
+ * unspecified to this extent: entry j either is not written or holds segment j as the table
+ * lists it (TRUNCATED_MESSAGE may list the segments before the one that runs past the data).
+ * No message ever writes into another message's row. */
 int capnp_packed_message_init_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint32_t max_segs, uint32_t* d_seg_count, uint64_t* d_seg_off,
                                     uint64_t* d_seg_len, int32_t* d_status, void* stream);
