@@ -1,5 +1,6 @@
 // kernels.h — internal launcher interface between the C-ABI (capnp_packed_abi.cpp)
-// and the gfx950 kernels (packed_kernels.hip). Not part of the public ABI.
+// and the gfx950 kernels (packed_kernels.hip and the headers under kernels/). Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -29,7 +30,6 @@ hipError_t release_stream(hipStream_t stream, int dev = -1);  // dev -1: the cur
 void stream_queue_info(hipStream_t stream, size_t* bytes, uint32_t* kept);
 uint32_t stream_context_count();  // caller streams with a library context (current device)
 
-// Reader.readPackedMessage over a batch of reader streams (reader.zig:84-156).
 // One unit (the single-buffer calls): the unit's status must be kStNeedFull (decode_one_status())
 // for decode_one; encode_one takes units of at most 512 words.
 int32_t decode_one_status();
@@ -39,6 +39,7 @@ hipError_t launch_decode_one(const uint8_t* in, const uint64_t* in_off, const ui
 hipError_t launch_encode_one(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out,
                              const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
                              bool write, hipStream_t stream);
+// Reader.readPackedMessage over a batch of reader streams (reader.zig:84-156).
 hipError_t launch_read_message(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
                                uint64_t* consumed, int32_t* status, hipStream_t stream);

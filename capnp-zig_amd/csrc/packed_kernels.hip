@@ -39,6 +39,15 @@
 //           passes), framing fused with encode (encode_message_kernel), Message.init
 //           (message_init_kernel), Message.validate (validate_kernel), synthetic data
 //           (generate_kernel) and the offsets scan.
+//
+// Where things are. Under kernels/, each header compiling on its own (make check-headers):
+//   kernels/common.h          wave / block constants, the ST_* and kSt* statuses
+//   kernels/device_helpers.h  loads, DPP wave scans, selectors and LUTs, partial stores, vmcnt_*
+//   kernels/generate_scan.h   generate_kernel and the offsets scan
+//   kernels/side_launch.h     host only: StreamCtx / SideLaunch, the launch flags
+// In this file, in the order of their definitions (which is the object's function order, so
+// neither a section nor an include may move): the banner-marked sections of the encoders, the
+// decoders, the class pass, validate, read-message and the framer, then the launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -57,392 +66,11 @@
 #include "class_ws.h"
 #include "kernels.h"
 
+// what every path shares
+#include "kernels/common.h"
+#include "kernels/device_helpers.h"
+
 namespace cpk {
-
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
-
-// ---- encode fast path ------------------------------------------------------
-constexpr uint32_t kEncMaxWords = 512;                 // 4 KiB unpacked unit
-constexpr uint32_t kEncRow = 80;                       // 64 B words + 16 B pad per lane row
-constexpr uint32_t kEncLds = 64 * kEncRow;             // 5120 B; reused for the packed output
-// max packed size of 512 words is 9*512+1 = 4609 B; + 16 B align slack + 16 B round-up <= 5120
-
-enum : int32_t {
-    ST_OK = CAPNP_PACKED_OK,
-    ST_SIZE = CAPNP_PACKED_INVALID_MESSAGE_SIZE,
-    ST_EOF = CAPNP_PACKED_UNEXPECTED_EOF,
-    ST_SPACE = CAPNP_PACKED_OUT_OF_SPACE,
-    ST_ARG = CAPNP_PACKED_INVALID_ARGUMENT,
-    ST_DEVERR = CAPNP_PACKED_DEVICE_ERROR,  // a kernel's own loop guard tripped (never expected)
-    // Reader.readPackedMessage (reader.zig:84-156)
-    ST_EOS = CAPNP_PACKED_END_OF_STREAM,
-    ST_SEGCOUNT = CAPNP_PACKED_INVALID_SEGMENT_COUNT,
-    ST_SEGLIMIT = CAPNP_PACKED_SEGMENT_COUNT_LIMIT_EXCEEDED,
-    ST_TOOLARGE = CAPNP_PACKED_MESSAGE_TOO_LARGE,
-    ST_OVERSHOOT = CAPNP_PACKED_INVALID_PACKED_MESSAGE,
-    ST_TRUNC = CAPNP_PACKED_TRUNCATED_MESSAGE,  // Message.init (message.zig:353/380)
-    // Message.validate (message.zig:699-969)
-    ST_EMPTY = CAPNP_PACKED_EMPTY_MESSAGE,
-    ST_NEST = CAPNP_PACKED_NESTING_LIMIT_EXCEEDED,
-    ST_SEGID = CAPNP_PACKED_INVALID_SEGMENT_ID,
-    ST_PTR = CAPNP_PACKED_INVALID_POINTER,
-    ST_OOB = CAPNP_PACKED_OUT_OF_BOUNDS,
-    ST_TRAV = CAPNP_PACKED_TRAVERSAL_LIMIT_EXCEEDED,
-    ST_FAR = CAPNP_PACKED_INVALID_FAR_POINTER,
-    ST_ICP = CAPNP_PACKED_INVALID_INLINE_COMPOSITE_POINTER,
-    ST_LIST = CAPNP_PACKED_LIST_TOO_LARGE,
-};
-// internal status between decode passes: the unit goes to a full (fallback) decoder
-constexpr int32_t kStNeedFull = 0x7FFF0001;
-constexpr int32_t kStNeedWalk = 0x7FFF0002;  // read-message: the one-pass walk could not take the unit
-constexpr int32_t kStNeedGate = 0x7FFF0003;  // read-message: walked (consumed known), records next
-constexpr int32_t kStWords = 0x7FFF0005;     // read-message: the words decoder's (read_header_kernel)
-constexpr uint64_t kRdWordsMax = 1024;       // read-message: framed words the words decoder takes
-// status of a long unit between its listing and its worker's result
-constexpr int32_t kStPending = CAPNP_PACKED_DEVICE_ERROR;
-
-// ---------------------------------------------------------------------------
-// small device helpers
-// ---------------------------------------------------------------------------
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// 16 readable bytes for load lanes that have nothing to stage, and 16 writable
-// bytes for the piece-record stores of lanes without a unit.
-__device__ __attribute__((aligned(16))) uint8_t cpk_dummy16[16];
-__device__ __attribute__((aligned(16))) uint8_t cpk_sink16[16];
-__device__ __attribute__((aligned(64))) uint8_t cpk_sink64[64];
-
-// 16-B load of data read for the last time (non-temporal). The fill pass's piece loads
-// use it (decode 2.42 -> 2.40 ms); encode's staging loads were slower with it.
-__device__ __forceinline__ uint4 load_nt(const void* p) {
-    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    return make_uint4(t.x, t.y, t.z, t.w);
-}
-
-// Ring loads of the lane-per-unit
-// decoders in inline asm, so hipcc neither turns them into FLAT instructions
-// (pointers that went through __shfl / LDS lose their address space, and FLAT counts on
-// lgkmcnt too: every LDS wait of the walk would wait for the prefetch) nor waits for them
-// itself (its own vmcnt(0) before the ring writes would also wait for the previous round's
-// stores). The kernels count them (s_waitcnt vmcnt(N)) and pin the loaded registers after
-// the wait (cdna_hip_programming.md §5.7 item 1, form ii).
-__device__ __forceinline__ void ds_gload16(u32x4& d, const void* p) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
-}
-
-// LDS-DMA: each lane's 16 B at gsrc straight into LDS at lds_base + 16 * lane (no VGPR
-// destination; count it with vmcnt, then a barrier before other waves read it). M0 is written
-// and restored in the same statement (cdna_hip_programming.md §5.7).
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_base) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
-}
-// the LDS byte address of a __shared__ object
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) uint8_t*)p);
-}
-
-// Order LDS traffic between lanes of ONE wave (the wave owns its LDS slice).
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
-
-// a 64-bit value from lane `src` (two 32-bit shuffles, zero-extended halves: an int | u64 would
-// sign-extend the low half)
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src, 64);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src, 64);
-    return (uint64_t)lo | ((uint64_t)hi << 32);
-}
-
-
-// Wave scans on DPP: row_shr:1/2/4/8 inside each 16-lane row, then row_bcast:15 and
-// row_bcast:31 across rows (gfx9). A lane a step does not reach keeps `ident`. No LDS
-// round trips (the ds_bpermute scans they replace cost ~6 LDS latencies in a row).
-template <int CTRL, int ROWS>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v, uint32_t ident) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)v, CTRL, ROWS, 0xF, false);
-}
-
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
-    v += dpp_mov<0x111, 0xF>(v, 0u);
-    v += dpp_mov<0x112, 0xF>(v, 0u);
-    v += dpp_mov<0x114, 0xF>(v, 0u);
-    v += dpp_mov<0x118, 0xF>(v, 0u);
-    v += dpp_mov<0x142, 0xA>(v, 0u);
-    v += dpp_mov<0x143, 0xC>(v, 0u);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
-    v = max(v, dpp_mov<0x111, 0xF>(v, 0u));
-    v = max(v, dpp_mov<0x112, 0xF>(v, 0u));
-    v = max(v, dpp_mov<0x114, 0xF>(v, 0u));
-    v = max(v, dpp_mov<0x118, 0xF>(v, 0u));
-    v = max(v, dpp_mov<0x142, 0xA>(v, 0u));
-    v = max(v, dpp_mov<0x143, 0xC>(v, 0u));
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_min(uint32_t v) {
-    v = min(v, dpp_mov<0x111, 0xF>(v, ~0u));
-    v = min(v, dpp_mov<0x112, 0xF>(v, ~0u));
-    v = min(v, dpp_mov<0x114, 0xF>(v, ~0u));
-    v = min(v, dpp_mov<0x118, 0xF>(v, ~0u));
-    v = min(v, dpp_mov<0x142, 0xA>(v, ~0u));
-    v = min(v, dpp_mov<0x143, 0xC>(v, ~0u));
-    return v;
-}
-
-// the wave's minimum / maximum, wave-uniform (the scan's last lane)
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-    return __builtin_amdgcn_readlane(wave_incl_min(v), kWave - 1);
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    return __builtin_amdgcn_readlane(wave_incl_max(v), kWave - 1);
-}
-
-// The DPP scan of a u64 sum, in place: per step moves on both halves and a 64-bit add. A macro,
-// so both functions below get the statements themselves (through a helper function, inlined,
-// the compiler split the adds and the kernels' code changed).
-#define CPK_SUM64_STEP(V, CTRL, ROWS)                                                           \
-    V += (uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)V, 0u) | ((uint64_t)dpp_mov<CTRL, ROWS>((uint32_t)(V >> 32), 0u) << 32)
-#define CPK_SUM64_SCAN(V)          \
-    CPK_SUM64_STEP(V, 0x111, 0xF); \
-    CPK_SUM64_STEP(V, 0x112, 0xF); \
-    CPK_SUM64_STEP(V, 0x114, 0xF); \
-    CPK_SUM64_STEP(V, 0x118, 0xF); \
-    CPK_SUM64_STEP(V, 0x142, 0xA); \
-    CPK_SUM64_STEP(V, 0x143, 0xC)
-// inclusive sum of a u64 over the wave
-__device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t v) {
-    CPK_SUM64_SCAN(v);
-    return v;
-}
-// sum of a u64 over the wave, wave-uniform
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    CPK_SUM64_SCAN(v);
-    return (uint64_t)__builtin_amdgcn_readlane((uint32_t)v, kWave - 1) |
-           ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), kWave - 1) << 32);
-}
-#undef CPK_SUM64_SCAN
-#undef CPK_SUM64_STEP
-
-// the previous lane's v (wave_shr:1); lane 0 gets ident
-__device__ __forceinline__ uint32_t wave_prev_lane(uint32_t v, uint32_t ident) { return dpp_mov<0x138, 0xF>(v, ident); }
-
-// Lane l - 1's v (lane 0: 0), read with every lane active: the asm pins the DPP move (and
-// the computation of v) in front of any branch on the lane, since a DPP read of a lane the
-// EXEC mask excludes returns that lane's stale register.
-__device__ __forceinline__ uint32_t fu_prev_lane(uint32_t v) {
-    uint32_t r = dpp_mov<0x138, 0xF>(v, 0u);
-    asm volatile("" : "+v"(r));
-    return r;
-}
-
-// v of the first lane above this one with `has` set, or `none` (encode_tile's run ends)
-__device__ __forceinline__ uint32_t next_break(bool has, uint32_t v, uint32_t lane, uint32_t none) {
-    const uint64_t above = (__builtin_amdgcn_ballot_w64(has) >> lane) >> 1;  // lanes > this one
-    const uint32_t src = above ? lane + 1u + (uint32_t)__builtin_ctzll(above) : lane;
-    const uint32_t r = (uint32_t)__shfl((int)v, (int)src, kWave);
-    return above ? r : none;
-}
-
-__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t l) {
-    return __builtin_amdgcn_readlane(v, l);
-}
-
-// Zero-byte tag of a little-endian word: bit k set <=> byte k != 0
-// (message.zig:257-262 builds the same tag byte-by-byte).
-__device__ __forceinline__ uint32_t nonzero_tag(uint64_t w) {
-    // byte k of c: bit 0 = byte k nonzero, bit 4 = byte k + 4 nonzero; the dot product with
-    // 2^k gathers them (one full-rate v_dot4 instead of two quarter-rate multiplies)
-    const uint32_t lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
-    const uint32_t yl = ((lo & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | lo, yh = ((hi & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | hi;
-    const uint32_t c = ((yl >> 7) & 0x01010101u) | ((yh >> 3) & 0x10101010u);
-    return __builtin_amdgcn_udot4(c, 0x08040201u, 0u, false);
-}
-
-// v_perm_b32 over the 8 bytes of d: selector byte r in 0..7 picks byte r, 0x0C gives 0.
-__device__ __forceinline__ uint64_t perm64(uint64_t d, uint64_t sel) {
-    uint32_t lo = (uint32_t)d, hi = (uint32_t)(d >> 32);
-    uint32_t a = __builtin_amdgcn_perm(hi, lo, (uint32_t)sel);
-    uint32_t b = __builtin_amdgcn_perm(hi, lo, (uint32_t)(sel >> 32));
-    return (uint64_t)a | ((uint64_t)b << 32);
-}
-
-// v_perm_b32 selector tables, built at compile time (a block copies one into LDS):
-//   compact: gathers the nonzero bytes of a word with tag t into bytes 0..popc-1
-//            (0x0C = zero above them);
-//   expand:  scatters popc(t) packed bytes back to the set-bit positions of t.
-struct alignas(16) SelLut {
-    uint64_t v[256];
-};
-constexpr SelLut make_sel_lut(bool expand) {
-    SelLut lut{};
-    for (uint32_t t = 0; t < 256; ++t) {
-        uint64_t sel = expand ? 0ull : 0x0C0C0C0C0C0C0C0CULL;
-        uint32_t r = 0;
-        for (uint32_t k = 0; k < 8; ++k) {
-            const bool set = (t >> k) & 1u;
-            if (expand) {
-                sel |= (set ? (uint64_t)(r++) : 0x0Cull) << (8 * k);
-            } else if (set) {
-                sel = (sel & ~(0xFFULL << (8 * r))) | ((uint64_t)k << (8 * r));
-                ++r;
-            }
-        }
-        lut.v[t] = sel;
-    }
-    return lut;
-}
-__device__ constexpr SelLut kCompactLut = make_sel_lut(false);
-__device__ constexpr SelLut kExpandLut = make_sel_lut(true);
-// The compact selector moved up one byte (byte 0 selects a zero byte): perm64(w, it) is the
-// tag's record payload at bytes 1..popc, ready to OR with the tag (encode_tile).
-__device__ __forceinline__ uint64_t compact_selector(uint32_t t) { return (kCompactLut.v[t] << 8) | 0x0Cull; }
-// the same as a table, for a copy into LDS by LDS-DMA (encode_kernel)
-constexpr SelLut make_compact_sel() {
-    SelLut l = make_sel_lut(false);
-    for (uint32_t t = 0; t < 256; ++t) l.v[t] = (l.v[t] << 8) | 0x0Cull;
-    return l;
-}
-__device__ constexpr SelLut kCompactSel = make_compact_sel();
-__device__ __forceinline__ uint64_t expand_selector(uint32_t t) { return kExpandLut.v[t]; }
-
-// Unaligned 8-byte read from an LDS byte array as two aligned ds_read_b64 and a branch-free
-// funnel shift (a byte-aligned ds_read_b64 is legal on gfx950 but measured ~2x slower in the
-// expand loop: the LDS splits it).
-__device__ __forceinline__ uint64_t lds_u64_at(const uint8_t* base, uint32_t p) {
-    const uint32_t a = p & ~7u;
-    const uint64_t lo = *reinterpret_cast<const uint64_t*>(base + a);
-    const uint64_t hi = *reinterpret_cast<const uint64_t*>(base + a + 8);
-    const uint32_t s = (p & 7u) * 8u;
-    return (lo >> s) | ((hi << 1) << (63u - s));
-}
-
-// 8-byte global loads: gload64 where p is known 8-aligned, ld_u64 / ld_u32 at any alignment
-// (gfx950 unaligned access: still one global_load_dwordx2 / dword).
-__device__ __forceinline__ uint64_t gload64(const uint8_t* p) {
-    return *reinterpret_cast<const uint64_t*>(p);
-}
-__device__ __forceinline__ uint64_t ld_u64(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
-// Stage nch 16-B chunks from global g[0 .. 16*nch) into lds[0 .. 16*nch):
-// lane l moves chunks l, l+64, ... Loads AND stores are unconditional, with the
-// chunk index clamped to nch-1 (a clamped lane re-writes the last chunk with the
-// same bytes), so the compiler cannot sink the loads into guarded blocks: all K
-// loads are in flight together and one vmcnt wait lands them.
-template <int K>
-__device__ __forceinline__ void stage_linear(uint8_t* lds, const uint8_t* g, uint32_t nch, uint32_t lane) {
-    if (nch == 0) return;
-    uint4 v[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const uint32_t c = min(lane + 64u * k, nch - 1);
-        v[k] = *reinterpret_cast<const uint4*>(g + 16 * (uint64_t)c);
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const uint32_t c = min(lane + 64u * k, nch - 1);
-        *reinterpret_cast<uint4*>(lds + 16 * c) = v[k];
-    }
-}
-
-// Bytes [lo, hi) (0 <= lo < hi <= 16) of a 16-B chunk (x0 = bytes 0-7, x1 = bytes 8-15)
-// whose 16-B aligned home is c16: naturally aligned 1/2/4/8-B stores, up to 8-B alignment
-// and then down from it (at most 8 predicated stores). A byte loop runs to the wave's
-// longest partial chunk (C5 small encode: ~100 us of 400).
-__device__ __forceinline__ void store_partial16(uint8_t* c16, uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1) {
-    auto put = [&](uint32_t sz) {  // bytes [lo, lo + sz), lo aligned to sz
-        const uint64_t v = lo < 8 ? x0 >> (8 * lo) : x1 >> (8 * (lo - 8));
-        uint8_t* const p = c16 + lo;
-        if (sz == 8) *reinterpret_cast<uint64_t*>(p) = v;
-        else if (sz == 4) *reinterpret_cast<uint32_t*>(p) = (uint32_t)v;
-        else if (sz == 2) *reinterpret_cast<uint16_t*>(p) = (uint16_t)v;
-        else *p = (uint8_t)v;
-        lo += sz;
-    };
-    if ((lo & 1) && lo + 1 <= hi) put(1);
-    if ((lo & 2) && lo + 2 <= hi) put(2);
-    if ((lo & 4) && lo + 4 <= hi) put(4);
-    if (lo + 8 <= hi) put(8);
-    if (lo + 4 <= hi) put(4);
-    if (lo + 2 <= hi) put(2);
-    if (lo + 1 <= hi) put(1);
-}
-// The same through global (address space 1) pointers, for kernels that count their LDS waits:
-// a generic pointer would make FLAT stores, which also count on lgkmcnt. (One template over the
-// pointer type changed the code of the kernels that use either, so both stay.)
-__device__ __forceinline__ void es_store_partial16(uint8_t* c16, uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1) {
-    typedef __attribute__((address_space(1))) uint8_t g8;
-    typedef __attribute__((address_space(1))) uint16_t g16;
-    typedef __attribute__((address_space(1))) uint32_t g32;
-    typedef __attribute__((address_space(1))) uint64_t g64;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(c16);
-    auto put = [&](uint32_t sz) {  // bytes [lo, lo + sz), lo aligned to sz
-        const uint64_t v = lo < 8 ? x0 >> (8 * lo) : x1 >> (8 * (lo - 8));
-        const uintptr_t p = base + lo;
-        if (sz == 8) *reinterpret_cast<g64*>(p) = v;
-        else if (sz == 4) *reinterpret_cast<g32*>(p) = (uint32_t)v;
-        else if (sz == 2) *reinterpret_cast<g16*>(p) = (uint16_t)v;
-        else *reinterpret_cast<g8*>(p) = (uint8_t)v;
-        lo += sz;
-    };
-    if ((lo & 1) && lo + 1 <= hi) put(1);
-    if ((lo & 2) && lo + 2 <= hi) put(2);
-    if ((lo & 4) && lo + 4 <= hi) put(4);
-    if (lo + 8 <= hi) put(8);
-    if (lo + 4 <= hi) put(4);
-    if (lo + 2 <= hi) put(2);
-    if (lo + 1 <= hi) put(1);
-}
-
-// s_waitcnt needs an immediate: wait until at most min(c, 8) / min(c, 63) vector-memory
-// operations are outstanding (a smaller count than the true number of younger operations only
-// waits longer). Two ladders: one function taking the cap compiled to different code in the
-// fill pass and the words decoder.
-__device__ __forceinline__ void vmcnt_at_most(uint32_t c) {
-    switch (c) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    }
-}
-__device__ __forceinline__ void vmcnt_at_most63(uint32_t c) {
-#define CPK_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-#define CPK_VM8(B) CPK_VM(B) CPK_VM(B + 1) CPK_VM(B + 2) CPK_VM(B + 3) CPK_VM(B + 4) CPK_VM(B + 5) CPK_VM(B + 6) CPK_VM(B + 7)
-    switch (c < 63u ? c : 63u) {
-        CPK_VM8(0) CPK_VM8(8) CPK_VM8(16) CPK_VM8(24) CPK_VM8(32) CPK_VM8(40) CPK_VM8(48)
-        CPK_VM(56) CPK_VM(57) CPK_VM(58) CPK_VM(59) CPK_VM(60) CPK_VM(61) CPK_VM(62)
-        default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-    }
-#undef CPK_VM8
-#undef CPK_VM
-}
 
 // ---------------------------------------------------------------------------
 // Serial encoder (one lane), any unit size. Restates message.zig:200-271 directly
@@ -6165,110 +5793,14 @@ __global__ __launch_bounds__(kWvBlock) void frame_walk_kernel(const uint8_t* __r
     }
 }
 
-// ---------------------------------------------------------------------------
-// synthetic generator and offset scan
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t unit, uint64_t word) {
-    uint64_t x = seed ^ (unit * 0x9E3779B97F4A7C15ULL) ^ (word * 0xC2B2AE3D27D4EB4FULL);
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
+}  // namespace cpk
 
-__global__ void generate_kernel(uint8_t* __restrict__ out, uint64_t n_units, uint64_t words_per_unit,
-                                uint64_t unit_base, uint64_t seed, uint32_t thr) {
-    const uint64_t total = n_units * words_per_unit;
-    for (uint64_t gw = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; gw < total;
-         gw += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t u = gw / words_per_unit, w = gw - u * words_per_unit;
-        uint64_t h = mix64(seed, unit_base + u, w);
-        uint64_t h2 = mix64(seed ^ 0xA5A5A5A5A5A5A5A5ULL, unit_base + u, w);
-        uint64_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            uint32_t r = (uint32_t)(h >> (8 * k)) & 0xFF;
-            uint32_t x = (uint32_t)(h2 >> (8 * k)) & 0xFF;
-            uint64_t b = (r < thr) ? 0 : (1 + x % 255);
-            v |= b << (8 * k);
-        }
-        *reinterpret_cast<uint64_t*>(out + 8 * gw) = v;
-    }
-}
+// the generator and the offsets scan, where their section was
+#include "kernels/generate_scan.h"
+// host only: the per-stream side-launch context and the launch policy flags
+#include "kernels/side_launch.h"
 
-constexpr int kScanItems = 8;
-constexpr int kScanTile = 256 * kScanItems;
-
-// block-local exclusive scan of u64 lengths; writes the block total to partial[blockIdx.x]
-__global__ __launch_bounds__(256) void scan_local_kernel(const uint64_t* __restrict__ len, uint32_t n,
-                                                         uint64_t* __restrict__ off,
-                                                         uint64_t* __restrict__ partial) {
-    __shared__ uint64_t wsum[4];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + tid * kScanItems;
-    uint64_t v[kScanItems];
-    uint64_t t = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        v[k] = (base + k < n) ? len[base + k] : 0;
-        t += v[k];
-    }
-    uint64_t x = t;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint64_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    uint64_t pre = 0;
-    for (uint32_t q = 0; q < wave; ++q) pre += wsum[q];
-    uint64_t run = pre + x - t;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < n) off[base + k] = run;
-        run += v[k];
-    }
-    if (tid == 255) partial[blockIdx.x] = pre + x;
-}
-
-// single-block exclusive scan of the partials (in place), then base added
-__global__ __launch_bounds__(1024) void scan_partials_kernel(uint64_t* __restrict__ partial, uint32_t np,
-                                                             uint64_t base, uint64_t* __restrict__ off_last,
-                                                             uint32_t n) {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry_s;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = base;
-    __syncthreads();
-    for (uint32_t b = 0; b < np; b += 1024) {
-        uint64_t v = (b + tid < np) ? partial[b + tid] : 0;
-        uint64_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            uint64_t y = __shfl_up(x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        uint64_t pre = carry_s;
-        for (uint32_t q = 0; q < wave; ++q) pre += wsum[q];
-        if (b + tid < np) partial[b + tid] = pre + x - v;
-        __syncthreads();
-        if (tid == 1023) carry_s = pre + x;
-        __syncthreads();
-    }
-    if (tid == 0) off_last[n] = carry_s;
-}
-
-__global__ __launch_bounds__(256) void scan_apply_kernel(uint64_t* __restrict__ off, uint32_t n,
-                                                         const uint64_t* __restrict__ partial) {
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-    const uint64_t add = partial[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k)
-        if (base + k < n) off[base + k] += add;
-}
+namespace cpk {
 
 // ---------------------------------------------------------------------------
 // launchers (kernels.h)
@@ -6280,50 +5812,6 @@ static inline uint32_t blocks_for(uint32_t n) { return (n + kWavesPerBlock - 1) 
 // striding over the long list, so they start beside a persistent small-unit grid (a block per
 // 256 units of the batch waited ~0.2 ms for slots on config C5, delaying the long-unit chain).
 static inline uint32_t list_blocks(uint32_t n) { return std::min((n + 255u) / 256u, 64u); }
-
-// Side stream for the long-unit kernels (encode_tiled_kernel, the decode fallback).
-// They select their units by a test on the unit's own lengths, so they need nothing
-// from the main kernels and run beside them: a batch whose few long units would
-// otherwise run alone after the main grid (config C5's tail) overlaps them with it.
-// fork(): the side stream waits for everything already on the caller's stream;
-// join(): the caller's stream waits for the side stream's kernels.
-//
-// Every (device, caller stream) pair has its own context: side stream, fork/join
-// events and long-unit queue, so batches on independent caller streams never wait
-// on each other, and a graph captured from one stream shares nothing with eager
-// work on another. The context's mutex keeps one caller's record/wait pairs and
-// queue reset together. A queue that has to grow is replaced by one of at least twice its
-// size (so a stream sees O(log n) replacements): the old one is freed after the stream
-// drains, unless a hipGraph capture used it (a captured graph may still reference it; it is
-// then kept until capnp_packed_stream_release). Growing is refused during a capture.
-// Callers that pass their own workspace (capnp_packed_*_batch_ws) use it as the
-// queue instead, so nothing of the library's is baked into their graphs.
-struct StreamCtx {
-    std::mutex mu;
-    hipStream_t s = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    hipStream_t s2 = nullptr;  // a second side stream (CAPNP_PACKED_LAUNCH_MID_SIDE_STREAM: C5's mid units)
-    hipEvent_t join2 = nullptr;
-    uint32_t* q = nullptr;  // class workspace (queue_bytes; class_ws.h)
-    uint64_t qcap = 0;
-    bool q_captured = false;         // q was used inside a hipGraph capture
-    std::vector<uint32_t*> retired;  // replaced queues a capture used (graphs may reference them)
-    ~StreamCtx() {
-        for (uint32_t* r : retired) (void)hipFree(r);
-        if (q) (void)hipFree(q);
-        if (s) (void)hipStreamDestroy(s);
-        if (s2) (void)hipStreamDestroy(s2);
-        if (fork) (void)hipEventDestroy(fork);
-        if (join) (void)hipEventDestroy(join);
-        if (join2) (void)hipEventDestroy(join2);
-    }
-};
-static std::mutex g_ctx_mu;
-// shared_ptr: a batch being enqueued keeps its context alive even if capnp_packed_stream_release
-// drops it from the map meanwhile (no use-after-free, whatever the callers do).
-static std::map<std::pair<int, uintptr_t>, std::shared_ptr<StreamCtx>> g_ctx;
-
-size_t queue_bytes(uint32_t n) { return class_ws_bytes(n); }
 
 // Resident blocks of a kernel across the device (hipOccupancy...), for persistent grids.
 template <typename K>
@@ -6345,19 +5833,7 @@ static void with_bool(bool b, F&& f) {
     else f(std::false_type{});
 }
 
-// Launch policy (capnp_packed_set_launch_flags, process-wide; no result depends on it):
-//   CAPNP_PACKED_LAUNCH_LONG_INLINE      the long-unit kernels run after the main grid on the
-//                                        caller's stream instead of on a side stream;
-//   CAPNP_PACKED_LAUNCH_MID_SIDE_STREAM  decode: a batch's mid units on a second side stream,
-//                                        launched before the small units' kernel, whose grid then
-//                                        takes 85% of its resident size. Round 3:
-//                                        C5 decode 0.678 -> 0.660 ms, but the headline (all mid
-//                                        units) 2.474 -> 2.499 ms from the extra fork and join.
-//   CAPNP_PACKED_LAUNCH_CLASS_SCAN       the class pass's scan as its own kernel (class_scan_kernel)
-//                                        also for batches of at most 1M units, whose scatter
-//                                        otherwise does it (the path larger batches always take).
-static std::atomic<uint32_t> g_launch_flags{0};
-uint32_t set_launch_flags(uint32_t f) { return g_launch_flags.exchange(f); }
+// readers of the launch policy flags (kernels/side_launch.h)
 static bool mid_side_stream() { return g_launch_flags.load(std::memory_order_relaxed) & CAPNP_PACKED_LAUNCH_MID_SIDE_STREAM; }
 static bool class_scan_launched() { return g_launch_flags.load(std::memory_order_relaxed) & CAPNP_PACKED_LAUNCH_CLASS_SCAN; }
 
@@ -6373,176 +5849,6 @@ static void launch_classes(const uint8_t* in, const uint64_t* in_off, const uint
     if (!fused) class_scan_kernel<<<1, 1024, 0, stream>>>(q, n, nb, words_min);
     class_scatter_kernel<KIND><<<nb, kClassBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, q, fused,
                                                                words_min);
-}
-
-class SideLaunch {
-  public:
-    SideLaunch(hipStream_t main, void* ws, size_t ws_bytes) : main_(main), ws_(ws), ws_bytes_(ws_bytes) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return;
-        {
-            std::lock_guard<std::mutex> g(g_ctx_mu);
-            std::shared_ptr<StreamCtx>& c = g_ctx[{dev, reinterpret_cast<uintptr_t>(main)}];
-            if (!c) c = std::make_shared<StreamCtx>();
-            ctx_ = c;
-        }
-        lock_ = std::unique_lock<std::mutex>(ctx_->mu);
-        if (g_launch_flags.load(std::memory_order_relaxed) & CAPNP_PACKED_LAUNCH_LONG_INLINE) {
-            side_ = main_;
-            ok_ = true;
-            return;
-        }
-        if (!ctx_->s) {
-            if (hipStreamCreateWithFlags(&ctx_->s, hipStreamNonBlocking) != hipSuccess) {
-                ctx_->s = nullptr;
-                return;
-            }
-            if (hipEventCreateWithFlags(&ctx_->fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&ctx_->join, hipEventDisableTiming) != hipSuccess) {
-                (void)hipStreamDestroy(ctx_->s);
-                ctx_->s = nullptr;
-                return;
-            }
-        }
-        side_ = ctx_->s;
-        ok_ = true;
-    }
-    // the stream the long-unit kernels go on (after fork())
-    hipStream_t stream() const { return side_; }
-    // The side stream waits for everything enqueued on the caller's stream so far.
-    hipError_t fork() {
-        if (!ok_ || side_ == main_ || forked_) return ok_ ? hipSuccess : hipErrorNotReady;
-        hipError_t e = hipEventRecord(ctx_->fork, main_);
-        if (e == hipSuccess) e = hipStreamWaitEvent(side_, ctx_->fork, 0);
-        if (e == hipSuccess) forked_ = true;
-        return e;
-    }
-    // The class workspace for a batch of n units (queue_bytes); launch_classes must run on it
-    // next (class_scan_kernel clears its counters); nullptr when the side stream or the queue
-    // cannot be set up.
-    uint32_t* queue(uint32_t n) {
-        if (!ok_) return nullptr;
-        uint32_t* q = nullptr;
-        if (ws_) {
-            if (ws_bytes_ < queue_bytes(n)) return nullptr;
-            q = static_cast<uint32_t*>(ws_);
-        } else {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(main_, &cs) != hipSuccess) return nullptr;
-            const bool capturing = cs != hipStreamCaptureStatusNone;
-            if (ctx_->qcap < n) {
-                if (capturing) return nullptr;
-                uint64_t cap = 2 * ctx_->qcap;
-                cap = cap < n ? n : cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap;
-                uint32_t* nq = nullptr;
-                if (hipMalloc(reinterpret_cast<void**>(&nq), queue_bytes((uint32_t)cap)) != hipSuccess) return nullptr;
-                if (ctx_->q) {
-                    if (ctx_->q_captured) {
-                        ctx_->retired.push_back(ctx_->q);
-                    } else {  // only this stream's batches used it (the side stream joins back)
-                        if (hipStreamSynchronize(main_) != hipSuccess) {
-                            (void)hipFree(nq);
-                            return nullptr;
-                        }
-                        (void)hipFree(ctx_->q);
-                    }
-                }
-                ctx_->q = nq;
-                ctx_->qcap = cap;
-                ctx_->q_captured = false;
-            }
-            ctx_->q_captured |= capturing;
-            q = ctx_->q;
-        }
-        return q;  // its head (counters, cursors) is cleared by class_scan_kernel
-    }
-    // A second side stream, forked like the first (after fork()); the caller's stream when it
-    // cannot be set up.
-    hipStream_t stream2() {
-        if (!forked_) return main_;
-        if (forked2_) return ctx_->s2;
-        if (!ctx_->s2) {
-            if (hipStreamCreateWithFlags(&ctx_->s2, hipStreamNonBlocking) != hipSuccess) {
-                ctx_->s2 = nullptr;
-                return main_;
-            }
-            if (hipEventCreateWithFlags(&ctx_->join2, hipEventDisableTiming) != hipSuccess) {
-                (void)hipStreamDestroy(ctx_->s2);
-                ctx_->s2 = nullptr;
-                return main_;
-            }
-        }
-        if (hipStreamWaitEvent(ctx_->s2, ctx_->fork, 0) != hipSuccess) return main_;
-        forked2_ = true;
-        return ctx_->s2;
-    }
-    hipError_t join() {
-        if (!forked_) return hipSuccess;
-        forked_ = false;
-        hipError_t e = hipEventRecord(ctx_->join, side_);
-        if (e == hipSuccess) e = hipStreamWaitEvent(main_, ctx_->join, 0);
-        if (forked2_) {
-            forked2_ = false;
-            hipError_t e2 = hipEventRecord(ctx_->join2, ctx_->s2);
-            if (e2 == hipSuccess) e2 = hipStreamWaitEvent(main_, ctx_->join2, 0);
-            if (e == hipSuccess) e = e2;
-        }
-        return e;
-    }
-    ~SideLaunch() { (void)join(); }
-
-  private:
-    hipStream_t main_;
-    void* ws_;
-    size_t ws_bytes_;
-    std::shared_ptr<StreamCtx> ctx_;  // held until after the join and the unlock
-    std::unique_lock<std::mutex> lock_;
-    hipStream_t side_ = nullptr;
-    bool ok_ = false, forked_ = false, forked2_ = false;
-};
-
-// Drop the library's context of a caller stream (its side stream, events and queues, also
-// those captured graphs used): after the stream's work is done and before it is destroyed.
-hipError_t release_stream(hipStream_t stream, int dev) {
-    hipError_t e = hipSuccess;
-    if (dev < 0) e = hipGetDevice(&dev);  // contexts are keyed by (device, stream)
-    if (e != hipSuccess) return e;
-    std::shared_ptr<StreamCtx> c;
-    {
-        std::lock_guard<std::mutex> g(g_ctx_mu);
-        auto it = g_ctx.find({dev, reinterpret_cast<uintptr_t>(stream)});
-        if (it == g_ctx.end()) return hipSuccess;
-        c = std::move(it->second);
-        g_ctx.erase(it);
-    }
-    std::lock_guard<std::mutex> g(c->mu);  // no batch of this stream is being enqueued
-    e = hipStreamSynchronize(stream);
-    if (e == hipSuccess && c->s) e = hipStreamSynchronize(c->s);
-    return e;  // ~StreamCtx frees the rest
-}
-
-// The per-stream queue the library holds for `stream`: its bytes, and how many replaced
-// queues it keeps because a capture used them (tests: growth stays bounded).
-void stream_queue_info(hipStream_t stream, size_t* bytes, uint32_t* kept) {
-    *bytes = 0;
-    *kept = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> g(g_ctx_mu);
-    auto it = g_ctx.find({dev, reinterpret_cast<uintptr_t>(stream)});
-    if (it == g_ctx.end()) return;
-    std::lock_guard<std::mutex> g2(it->second->mu);
-    *bytes = it->second->q ? queue_bytes((uint32_t)it->second->qcap) : 0;
-    *kept = (uint32_t)it->second->retired.size();
-}
-
-uint32_t stream_context_count() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> g(g_ctx_mu);
-    uint32_t k = 0;
-    for (const auto& kv : g_ctx) k += kv.first.first == dev;
-    return k;
 }
 
 hipError_t launch_encode(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Dev-only host model of decode_stream_kernel's per-lane logic (packed_kernels.hip, DESIGN.md
-§2.3b): the 80-B ring per round (block k-1's last piece + block k, stale past the last block),
+"""Dev-only host model of decode_stream_kernel's per-lane logic (removed in round 5; its source
+is csrc/dev_decoders.inc at 869fccf): the 80-B ring per round (block k-1's last
+piece + block k, stale past the last block),
 the walk steps with their u16 entries (tag << 8 | ring offset of the word's bytes), zero-run
 jobs, words past the capacity counted only, and the store phase's expansion from the ring.
 Checked against the oracle (tests/oracle.py, message.zig:88-191) on random and adversarial

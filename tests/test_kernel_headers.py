@@ -1,0 +1,28 @@
+"""Every kernel header (capnp-zig_amd/csrc/kernels/*.h) compiles on its own: it includes what it
+uses, so the dependencies each header names in its opening comment are the ones the compiler
+sees. Runs the Makefile's check-headers command (hipcc -fsyntax-only for gfx950, no GPU needed)
+on one header per case."""
+import glob
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "capnp-zig_amd")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(PKG, "csrc", "kernels", "*.h")))
+
+
+def test_headers_found():
+    assert HEADERS, "no header under capnp-zig_amd/csrc/kernels/"
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_compiles_alone(header):
+    if shutil.which(HIPCC) is None:
+        pytest.skip("no hipcc on this machine")
+    run = subprocess.run(["make", "-s", "-C", PKG, "check-headers", "HIPCC=" + HIPCC,
+                          "KHDRS=csrc/kernels/" + header], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
