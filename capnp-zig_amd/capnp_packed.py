@@ -184,6 +184,9 @@ SIGNATURES = {
     "capnp_packed_encode_dense_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64,
                                                        ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _sz,
                                                        _vp]),
+    "capnp_packed_split_workspace_bytes": (_sz, [ctypes.c_uint32, ctypes.c_uint64]),
+    "capnp_packed_split_streams": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "capnp_packed_decoded_size": (ctypes.c_int, [_vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_decode": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
     "capnp_packed_encode_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1050,6 +1053,90 @@ def read_message_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, c
     _raise(lib().capnp_packed_read_message_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out),
                                                  _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(consumed),
                                                  _ptr(status), _stream(stream)), "read_message_batch")
+
+
+def split_workspace(n: int, in_bytes_bound: int, device="cuda"):
+    """Device workspace of split_streams (capnp_packed_split_workspace_bytes) for n streams of
+    at most in_bytes_bound packed bytes in all; the call sets it up itself. The bound sizes the
+    window tables only: a smaller one (0 included) costs time on long streams, never results.
+    Two calls in flight must not share one."""
+    nbytes = lib().capnp_packed_split_workspace_bytes(n, in_bytes_bound)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def split_streams(d_in, in_off, in_len, msg_first, msg_off, msg_len, msg_framed, consumed, status,
+                  msg_stream=None, ws=None, stream=None) -> None:
+    """Dense streams of packed messages split into their messages (capnp_packed_split_streams):
+    stream s = d_in[in_off[s] : in_off[s] + in_len[s]] is what repeated Reader.readPackedMessage
+    calls on one reader would consume. msg_first (n + 1 entries) gets the whole messages before
+    each stream (msg_first[n]: the total); row k of the tables (msg_off.numel() rows; rows past
+    that are counted, not written) gets the message's offset in d_in, its packed and its framed
+    length, msg_stream[k] (int32, optional) its stream. consumed / status are per stream.
+    (msg_off, msg_len) are a decode_batch's or read_message_batch's (in_off, in_len);
+    lengths_to_offsets(msg_framed) its dense output layout. msg_off / msg_len / msg_framed may
+    all be None (counts only). ws: a split_workspace() tensor (None: one without window tables
+    is allocated for the call)."""
+    n = _units(in_off, in_len, consumed, status)
+    if msg_first is None or msg_first.numel() < n + 1:
+        raise InvalidArgument(f"msg_first needs {n + 1} entries for {n} streams")
+    tables = (msg_off, msg_len, msg_framed)
+    if any(t is None for t in tables) and not all(t is None for t in tables):
+        raise InvalidArgument("msg_off, msg_len and msg_framed go together")
+    max_msgs = 0 if msg_off is None else min(t.numel() for t in tables)
+    if msg_stream is not None and msg_stream.numel() < max_msgs:
+        raise InvalidArgument(f"msg_stream has {msg_stream.numel()} entries for {max_msgs} rows")
+    if ws is None and n:
+        ws = split_workspace(n, 0, device=in_off.device)
+    _raise(lib().capnp_packed_split_streams(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, max_msgs, _ptr(msg_first),
+                                            _ptr(msg_off), _ptr(msg_len), _ptr(msg_framed), _ptr(msg_stream),
+                                            _ptr(consumed), _ptr(status), *_ws(ws), _stream(stream)),
+           "split_streams")
+
+
+def read_packed_messages(data, device="cuda") -> tuple:
+    """Every whole message of a host packed stream: (frames, consumed, status_name), what calling
+    Reader.readPackedMessage on one reader until it fails or runs dry gives. frames: the framed
+    bytes of the whole messages in order; consumed: their packed bytes; status_name: "OK" when
+    every byte was consumed, else the name of the status the loop stopped with (the frames
+    before it are still returned). One upload of the bytes, split_streams -> lengths_to_offsets
+    -> decode_batch on the device, one download of all frames (plus the two totals that size
+    the tables and the download)."""
+    data = bytes(data)
+    if not data:
+        return [], 0, lib().capnp_packed_status_name(OK).decode()
+    dev = torch.device(device)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+    in_off = torch.zeros(1, dtype=torch.int64, device=dev)
+    in_len = torch.full((1,), len(data), dtype=torch.int64, device=dev)
+    first = torch.empty(2, dtype=torch.int64, device=dev)
+    consumed = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = split_workspace(1, len(data), device=dev)
+    rows = len(data) // 64 + 16  # a first guess; msg_first[1] is the count a retry needs
+    while True:
+        tab = torch.empty((3, rows), dtype=torch.int64, device=dev)
+        split_streams(d_in, in_off, in_len, first, tab[0], tab[1], tab[2], consumed, status, ws=ws)
+        total = int(first[1].item())
+        if total <= rows:
+            break
+        rows = total
+    st_name = lib().capnp_packed_status_name(int(status.item())).decode()
+    used = int(consumed.item())
+    if total == 0:
+        return [], used, st_name
+    framed = tab[2][:total]
+    out_off = lengths_to_offsets(framed)
+    nbytes = int(out_off[total].item())
+    d_out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out_len = torch.empty(total, dtype=torch.int64, device=dev)
+    dst = torch.empty(total, dtype=torch.int32, device=dev)
+    decode_batch(d_in, tab[0][:total], tab[1][:total], d_out, out_off, framed, out_len, dst)
+    host = d_out.cpu().numpy().tobytes()
+    bad = int((dst != OK).sum().item())
+    if bad:
+        raise DeviceError(f"read_packed_messages: {bad} of {total} split messages failed to decode")
+    ends = out_off.cpu().tolist()
+    return [host[ends[k]:ends[k + 1]] for k in range(total)], used, st_name
 
 
 def encode_message_batch(seg_ptr, seg_len, seg_first, seg_count, d_out, out_off, out_cap, out_len, status,

@@ -644,6 +644,34 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
                     "dense encode launch");
 }
 
+size_t capnp_packed_split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound) {
+    return cpk::split_workspace_bytes(n, in_bytes_bound);
+}
+
+// Every argument check answers before any device work.
+int capnp_packed_split_streams(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
+                               uint64_t max_msgs, uint64_t* d_msg_first, uint64_t* d_msg_off, uint64_t* d_msg_len,
+                               uint64_t* d_msg_framed, uint32_t* d_msg_stream, uint64_t* d_consumed,
+                               int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!d_msg_first) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null d_msg_first");
+    if (n) {
+        if (!d_in_off || !d_in_len || !d_consumed || !d_status)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+        if (max_msgs && (!d_msg_off || !d_msg_len || !d_msg_framed))
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null message table");
+        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the splitter needs a workspace");
+        int st = check_ws(d_workspace, workspace_bytes, cpk::split_workspace_bytes(n, 0),
+                          "workspace smaller than capnp_packed_split_workspace_bytes(n, 0)");
+        if (st) return st;
+    }
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_split_streams(d_in, d_in_off, d_in_len, n, max_msgs, d_msg_first, d_msg_off, d_msg_len,
+                                              d_msg_framed, d_msg_stream, d_consumed, d_status, d_workspace,
+                                              workspace_bytes, static_cast<hipStream_t>(stream)),
+                    "split launch");
+}
+
 int capnp_packed_encoded_size_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint64_t* d_out_len, int32_t* d_status, void* stream) {
     return codec_batch(cpk::launch_encode, "encode-size launch", d_in, d_in_off, d_in_len, n, nullptr, nullptr, nullptr,

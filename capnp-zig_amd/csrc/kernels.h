@@ -66,6 +66,17 @@ hipError_t launch_frame_walk(const uint8_t* arena, const uint32_t* list, uint32_
                              const uint32_t* spec_first, const uint32_t* spec_count, const uint64_t* spec_off,
                              const uint64_t* spec_len, hipStream_t stream);
 
+// Dense streams split into their packed messages (capnp_packed_split_streams):
+// a wave per stream walks message after message, stateless. ws: at least
+// split_workspace_bytes(n, 0) bytes, 256-B aligned, set up by a kernel on every call; what it
+// holds beyond that is the window table (as many windows as fit, at most framer_window_cap(n)).
+// max_msgs 0: counts, consumed and statuses only.
+size_t split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound);
+hipError_t launch_split_streams(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                                uint64_t max_msgs, uint64_t* msg_first, uint64_t* msg_off, uint64_t* msg_len,
+                                uint64_t* msg_framed, uint32_t* msg_stream, uint64_t* consumed, int32_t* status,
+                                void* ws, size_t ws_bytes, hipStream_t stream);
+
 // MessageBuilder.toPackedBytes from segment lists (message.zig:2123-2179).
 hipError_t launch_encode_message(const uint64_t* seg_ptr, const uint64_t* seg_len, const uint32_t* seg_first,
                                  const uint32_t* seg_count, uint32_t n, uint8_t* out, const uint64_t* out_off,

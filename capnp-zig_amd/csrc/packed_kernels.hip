@@ -5631,6 +5631,96 @@ __global__ __launch_bounds__(256) void copy_jobs_kernel(const uint64_t* __restri
     }
 }
 
+// One message's walk towards its end, by a wave (split_walk_kernel; frame_walk_kernel below keeps
+// the same loop inline, with its session state around it, so that its code stays as it was): the
+// message has Lw framed words, of which wd are counted at packed byte x of the stream src[0, P).
+// Windows lie at fixed positions x0 + j * kWvWin; with a spec table (window_spec_kernel over
+// [x0, P), computed for all windows at once; sf: the stream's first entry, kWinNone: no table) a
+// window the message neither ends in nor runs out of bytes in is crossed by a table lookup: its
+// exit and word count from the entry d the chain arrives at. Every trip of the loop moves x
+// forward or leaves. Returns ST_OK with x at the message's end (the first record after which the
+// words reach Lw: reader.zig:90-93 and 146-153), ST_OVERSHOOT when that record produced more, or
+// ST_EOS when the bytes end first (x / wd then stand after the last complete record).
+__device__ __forceinline__ int32_t wv_walk_message(uint8_t* pk, uint8_t* mk, const uint8_t* src, uint64_t P,
+                                                   uint64_t x0, const WinEnt* __restrict__ spec, uint32_t sf,
+                                                   uint64_t Lw, uint64_t& x, uint64_t& wd, uint32_t lane) {
+    while (x < P) {
+        const uint64_t j = (x - x0) / kWvWin;
+        const uint64_t Xj = x0 + j * kWvWin;
+        const uint32_t d = (uint32_t)(x - Xj);
+        if (sf != kWinNone) {
+            const WinEnt* const e = spec + sf + j;
+            const uint64_t vm = e->valid;
+            if (d < kWinD && ((vm >> d) & 1)) {
+                const int32_t dl = e->delta[d];
+                const uint32_t ex = e->exit;
+                if (dl != kDeltaEof && ex != kEOFX) {
+                    const uint64_t words = (uint64_t)((int64_t)e->total + dl);
+                    if (wd + words < Lw) {
+                        wd += words;
+                        x = Xj + ex;
+                        continue;
+                    }
+                }
+            }
+        }
+        // the window walked exactly from entry d: the message ends in it, the held bytes
+        // end in it, or the table does not know entry d
+        const WvWin w = wv_stage(pk, mk, src, P, Xj, lane);
+        uint32_t ent, cs, ce;
+        const uint32_t xw = wv_resolve(pk, mk, w, d, lane, ent, cs, ce);
+        // the lane's complete records (a record past the held bytes ends the chain)
+        uint32_t words = 0, stop = kEOFX;
+        for (uint32_t r = ent; r < ce;) {
+            uint32_t t = pk[w.sh + r];
+            uint32_t b1 = pk[w.sh + r + 1];
+            uint32_t c9 = pk[w.sh + r + 9];
+            asm volatile("" : "+v"(t), "+v"(b1), "+v"(c9));
+            const uint32_t len = wv_len(t, c9);
+            if ((uint64_t)r + len > w.rem) {
+                stop = r;
+                break;
+            }
+            words += 1u + ((t == 0u) ? b1 : 0u) + ((t == 0xFFu) ? c9 : 0u);
+            r += len;
+        }
+        const uint32_t incl = wave_incl_sum(words);
+        const uint32_t total = readlane(incl, kWave - 1);
+        if (wd + total >= Lw) {  // the message ends in this window
+            const uint64_t bm = __ballot(wd + incl >= Lw);
+            const uint32_t f = (uint32_t)__builtin_ctzll(bm);
+            uint32_t end = 0, over = 0;
+            if (lane == f) {
+                uint64_t acc = wd + incl - words;
+                for (uint32_t r = ent;;) {
+                    const uint32_t t = pk[w.sh + r], b1 = pk[w.sh + r + 1], c9 = pk[w.sh + r + 9];
+                    acc += 1u + ((t == 0u) ? b1 : 0u) + ((t == 0xFFu) ? c9 : 0u);
+                    r += wv_len(t, c9);
+                    if (acc >= Lw) {
+                        end = r;
+                        over = acc != Lw;
+                        break;
+                    }
+                }
+            }
+            end = readlane(end, f);
+            over = readlane(over, f);
+            if (over) return ST_OVERSHOOT;
+            x = Xj + end;
+            return ST_OK;
+        }
+        if (xw == kEOFX) {  // the chain stops at a record the bytes do not hold yet
+            const uint64_t bm = __ballot(stop != kEOFX);
+            x = bm ? Xj + readlane(stop, (uint32_t)__builtin_ctzll(bm)) : x;
+            wd += total;
+            return ST_EOS;
+        }
+        x = Xj + xw;
+        wd += total;
+    }
+    return ST_EOS;
+}
+
 // The walk of a connection's held bytes, message after message: a wave per
 // listed connection. Each message's framed length comes from its header (packed_header on lane
 // 0; need[c] already holds it when the previous read decoded the header), then the walk to its
@@ -5789,6 +5879,127 @@ __global__ __launch_bounds__(kWvBlock) void frame_walk_kernel(const uint8_t* __r
             Ws[c] = st == ST_EOS ? wd : 0;
             status[c] = st;
             cnt[i] = nm;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Dense streams of packed messages split into their messages (capnp_packed_split_streams,
+// DESIGN.md §2.11): what repeated Reader.readPackedMessage calls on one reader consume
+// (reader.zig:84-156), for n streams at once and with no state between calls.
+//   split_init_kernel     clears the spec block's head (the windows counter);
+//   split_windows_kernel  lists the windows of every stream longer than one window in the spec
+//                         block's window table, as long as they fit (first[s]: the stream's first
+//                         entry, kWinNone: no table; such a stream is walked window by window);
+//   split_clamp_kernel    the counter never names more windows than the table holds;
+//   window_spec_kernel    every listed window's table, in parallel (as for the framer);
+//   split_walk_kernel     <false>: a wave per stream counts its whole messages and writes
+//                         consumed / status; the counts are scanned into msg_first (scan_*_kernel);
+//                         <true>: the same walk again writes the rows at msg_first[s] + k.
+// A message's start is only known from its predecessor's header and end, so inside one stream
+// the walk is serial from message to message (parallel inside a window, a lookup per window
+// crossed); the parallelism is across streams. Every loop moves its packed position forward or
+// leaves; no wave waits for another.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kSplitMaxStream = CAPNP_PACKED_SPLIT_MAX_STREAM_BYTES;
+
+__global__ __launch_bounds__(kQHead) void split_init_kernel(uint32_t* q) { q[threadIdx.x] = 0; }
+
+__global__ __launch_bounds__(256) void split_windows_kernel(const uint64_t* __restrict__ in_len, uint32_t n,
+                                                            uint32_t* q, uint64_t cap,
+                                                            uint32_t* __restrict__ first) {
+    WinEnt* const e = win_tab(q, n);
+    const uint32_t lane = lane_id();
+    for (uint64_t i0 = blockIdx.x * 256 + (threadIdx.x & ~(kWave - 1)); i0 < n; i0 += (uint64_t)gridDim.x * 256) {
+        const uint64_t s = i0 + lane;
+        const bool v = s < n;
+        const uint64_t P = v ? in_len[s] : 0ull;
+        const uint64_t k = (P > kWvWin && P <= kSplitMaxStream) ? (P + kWvWin - 1) / kWvWin : 0ull;
+        const uint64_t want = k <= cap ? k : 0ull;
+        const uint64_t r = wave_reserve(q_tiles(q), want);
+        const bool fits = want != 0 && r + want <= cap;
+        if (want != 0 && !fits)
+            for (uint64_t j = r; j < cap; ++j) e[j].unit = kTileSkip;  // reserved past the end: unused
+        if (v) first[s] = fits ? (uint32_t)r : kWinNone;
+        // the wave fills one stream's entries after the other
+        for (uint64_t bm = __ballot(fits); bm; bm &= bm - 1) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(bm);
+            const uint64_t kl = __shfl(want, l, kWave), rl = __shfl(r, l, kWave);
+            for (uint64_t j = lane; j < kl; j += kWave) {
+                e[rl + j].unit = (uint32_t)(i0 + l);
+                e[rl + j].first = (uint32_t)rl;
+            }
+        }
+    }
+}
+
+__global__ void split_clamp_kernel(uint32_t* q, uint64_t cap) {
+    if (*q_tiles(q) > cap) *q_tiles(q) = cap;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(kWvBlock) void split_walk_kernel(
+    const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint64_t* __restrict__ in_len,
+    uint32_t n, const WinEnt* __restrict__ spec, const uint32_t* __restrict__ first, uint64_t* __restrict__ cnt,
+    uint64_t* __restrict__ consumed, int32_t* __restrict__ status, const uint64_t* __restrict__ msg_first,
+    uint64_t max_msgs, uint64_t* __restrict__ msg_off, uint64_t* __restrict__ msg_len,
+    uint64_t* __restrict__ msg_framed, uint32_t* __restrict__ msg_stream) {
+    __shared__ __attribute__((aligned(16))) uint8_t pk_all[kWvWaves * kWvPk];
+    __shared__ __attribute__((aligned(16))) uint8_t mk_all[kWvWaves * kWvWin];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint8_t* const pk = pk_all + wave * kWvPk;
+    uint8_t* const mk = mk_all + wave * kWvWin;
+    for (uint64_t s = blockIdx.x * kWvWaves + wave; s < n; s += (uint64_t)gridDim.x * kWvWaves) {
+        const uint64_t off = in_off[s], P = in_len[s];
+        uint64_t base = 0, rows = 0;  // EMIT: the stream's first row and the rows it may write
+        if (EMIT) {
+            base = msg_first[s];
+            if (base >= max_msgs) continue;
+            rows = min(cnt[s], max_msgs - base);
+            if (rows == 0) continue;
+        }
+        if (P > kSplitMaxStream) {
+            if (!EMIT && lane == 0) {
+                cnt[s] = 0;
+                consumed[s] = 0;
+                status[s] = ST_ARG;
+            }
+            continue;
+        }
+        const uint8_t* const src = in + off;
+        const uint32_t sf = first ? __builtin_amdgcn_readfirstlane(first[s]) : kWinNone;
+        uint64_t m0 = 0, nm = 0;  // the current message's first packed byte; whole messages so far
+        int32_t st = ST_OK;
+        for (;;) {
+            if (EMIT && nm == rows) break;
+            if (m0 == P) break;  // every byte consumed (an empty stream at once): OK
+            uint64_t nd = 0;
+            int32_t hs = ST_EOS;
+            if (lane == 0) hs = packed_header(src + m0, P - m0, nd);
+            hs = (int32_t)readlane((uint32_t)hs, 0);
+            if (hs != ST_OK) {
+                st = hs;
+                break;
+            }
+            const uint64_t L = ((uint64_t)readlane((uint32_t)(nd >> 32), 0) << 32) | readlane((uint32_t)nd, 0);
+            uint64_t x = m0, wd = 0;  // the header's records count towards the framed words
+            st = wv_walk_message(pk, mk, src, P, 0, spec, sf, L >> 3, x, wd, lane);
+            if (st != ST_OK) break;
+            if (EMIT && lane == 0) {
+                const uint64_t k = base + nm;
+                msg_off[k] = off + m0;
+                msg_len[k] = x - m0;
+                msg_framed[k] = L;
+                if (msg_stream) msg_stream[k] = (uint32_t)s;
+            }
+            ++nm;
+            m0 = x;
+        }
+        if (!EMIT && lane == 0) {
+            cnt[s] = nm;
+            consumed[s] = m0;
+            status[s] = st;
         }
     }
 }
@@ -6247,6 +6458,70 @@ hipError_t launch_frame_walk(const uint8_t* arena, const uint32_t* list, uint32_
     const uint32_t blocks = std::min((nl + kWvWaves - 1) / kWvWaves, res);
     frame_walk_kernel<<<blocks, kWvBlock, 0, stream>>>(arena, list, nl, base, avail, need, X, W, status, spec,
                                                         spec ? spec_first : nullptr, M, cnt, tab);
+    return hipGetLastError();
+}
+
+// The splitter's workspace for n streams: the per-stream message counts (u64, the scan's input),
+// the scan's scratch, each stream's first window-table entry (u32), then, 256-B aligned, a spec
+// block (class_ws.h: framer_spec_ws_bytes) of n units whose window table takes the rest.
+struct SplitWs {
+    uint64_t* cnt;
+    uint64_t* scan;
+    uint32_t* first;
+    uint32_t* q;
+    uint64_t cap;  // windows the table holds
+};
+static size_t split_q_off(uint32_t n) {
+    const size_t fixed = 8ull * n + scan_scratch_bytes(n) + 4ull * n;
+    return (fixed + 255) & ~(size_t)255;
+}
+static SplitWs split_ws(void* ws, size_t ws_bytes, uint32_t n) {
+    uint8_t* const p = static_cast<uint8_t*>(ws);
+    SplitWs w;
+    w.cnt = reinterpret_cast<uint64_t*>(p);
+    w.scan = w.cnt + n;
+    w.first = reinterpret_cast<uint32_t*>(p + 8ull * n + scan_scratch_bytes(n));
+    w.q = reinterpret_cast<uint32_t*>(p + split_q_off(n));
+    const size_t head = split_q_off(n) + framer_spec_ws_bytes(n, 0);
+    w.cap = ws_bytes > head ? std::min<uint64_t>((ws_bytes - head) / kWinEntBytes, win_cap(n)) : 0;
+    return w;
+}
+
+// in_bytes_bound packed bytes hold at most in_bytes_bound / kWvWin streams of more than one
+// window, and those at most one window more each than their bytes fill.
+size_t split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound) {
+    if (n == 0) return 0;
+    const uint64_t full = in_bytes_bound / kWvWin;
+    const uint64_t windows = std::min<uint64_t>(full + std::min<uint64_t>(full, n), win_cap(n));
+    return split_q_off(n) + framer_spec_ws_bytes(n, windows);
+}
+
+hipError_t launch_split_streams(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                                uint64_t max_msgs, uint64_t* msg_first, uint64_t* msg_off, uint64_t* msg_len,
+                                uint64_t* msg_framed, uint32_t* msg_stream, uint64_t* consumed, int32_t* status,
+                                void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (n == 0) return launch_scan(nullptr, 0, 0, msg_first, nullptr, stream);  // msg_first[0] = 0
+    const SplitWs w = split_ws(ws, ws_bytes, n);
+    const WinEnt* spec = nullptr;
+    if (w.cap) {
+        split_init_kernel<<<1, kQHead, 0, stream>>>(w.q);
+        split_windows_kernel<<<std::min((n + 255u) / 256u, 1024u), 256, 0, stream>>>(in_len, n, w.q, w.cap, w.first);
+        split_clamp_kernel<<<1, 1, 0, stream>>>(w.q, w.cap);
+        static const uint32_t spec_res = resident_blocks(window_spec_kernel, kWvBlock, 4);
+        const uint32_t sb = (uint32_t)std::min<uint64_t>((w.cap + kWvWaves - 1) / kWvWaves, spec_res);
+        window_spec_kernel<<<sb, kWvBlock, 0, stream>>>(in, in_off, in_len, n, w.q);
+        spec = reinterpret_cast<const WinEnt*>(w.q + win_tab_off(n));
+    }
+    static const uint32_t res = resident_blocks(split_walk_kernel<false>, kWvBlock, 2);
+    const uint32_t blocks = std::min((n + kWvWaves - 1) / kWvWaves, res);
+    split_walk_kernel<false><<<blocks, kWvBlock, 0, stream>>>(in, in_off, in_len, n, spec, spec ? w.first : nullptr,
+                                                             w.cnt, consumed, status, nullptr, 0, nullptr, nullptr,
+                                                             nullptr, nullptr);
+    hipError_t e = launch_scan(w.cnt, n, 0, msg_first, w.scan, stream);
+    if (e != hipSuccess || max_msgs == 0) return e;
+    split_walk_kernel<true><<<blocks, kWvBlock, 0, stream>>>(in, in_off, in_len, n, spec, spec ? w.first : nullptr,
+                                                            w.cnt, nullptr, nullptr, msg_first, max_msgs, msg_off,
+                                                            msg_len, msg_framed, msg_stream);
     return hipGetLastError();
 }
 

@@ -48,7 +48,9 @@ extern "C" {
  *     capnp_packed_encode_batch_dialect, capnp_packed_encode_message_batch_dialect (the opt-in
  *     C++-canonical encoder). Nothing that existed changed.
  *   2, additions only: capnp_packed_encode_dense_workspace_bytes and
- *     capnp_packed_encode_dense_batch (the batch form of writePackedTo). */
+ *     capnp_packed_encode_dense_batch (the batch form of writePackedTo).
+ *   2, additions only: capnp_packed_split_workspace_bytes and capnp_packed_split_streams (dense
+ *     streams of packed messages split into their messages: the reader's half of the above). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -421,6 +423,65 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
                                     uint64_t* d_out_off /* n + 1 */, uint64_t* d_out_len /* n */,
                                     int32_t* d_status /* n */, uint32_t dialect, void* d_workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Dense streams of packed messages split into their messages: what repeated
+ * Reader.readPackedMessage calls on one reader consume (reader.zig:84-156), for n streams in
+ * one call and without knowing where any message starts. Stream s is
+ * d_in[d_in_off[s] .. + d_in_len[s]), at any byte alignment: a file written by
+ * `capnp convert binary:packed`, a log of writePackedTo calls, or
+ * capnp_packed_encode_dense_batch's stream without its offsets.
+ * Per stream: the whole messages in order; d_consumed[s] = the packed bytes of those whole
+ * messages (where the loop stopped); d_status[s] =
+ *   OK                    every byte consumed (an empty stream: OK, 0 messages);
+ *   END_OF_STREAM         the bytes end inside a message;
+ *   INVALID_SEGMENT_COUNT, SEGMENT_COUNT_LIMIT_EXCEEDED, MESSAGE_TOO_LARGE,
+ *   INVALID_PACKED_MESSAGE  the error of the message the loop stopped in; the messages before
+ *                         it are still listed;
+ *   INVALID_ARGUMENT      the stream has more than CAPNP_PACKED_SPLIT_MAX_STREAM_BYTES bytes: 0
+ *                         messages, 0 consumed, none of its bytes read.
+ * Message table: d_msg_first[s] = whole messages in the streams before s, d_msg_first[n] = the
+ * total (n + 1 entries). Stream s owns rows [d_msg_first[s], d_msg_first[s + 1]) in stream
+ * order; row k: d_msg_off[k] the message's first packed byte as an offset from d_in (not from
+ * the stream), d_msg_len[k] its packed length, d_msg_framed[k] its framed length,
+ * d_msg_stream[k] = s (d_msg_stream may be NULL). (d_msg_off, d_msg_len) pass unchanged as the
+ * (in_off, in_len) of capnp_packed_decode_batch / capnp_packed_read_message_batch, and
+ * capnp_packed_lengths_to_offsets(d_msg_framed) gives dense output offsets and exact
+ * capacities.
+ * Too few rows: d_msg_first always holds the full counts, so d_msg_first[n] is the max_msgs a
+ * retry needs; rows k >= max_msgs are not written, nothing at or past index max_msgs of any
+ * table is touched, statuses and d_consumed are unaffected, and the call still returns OK
+ * (max_msgs 0: the tables may be NULL; counts, consumed and statuses only).
+ * Reads: no result depends on a byte outside a stream's [off, off + len), and a message cut off
+ * at a stream's end is never completed from the next stream's bytes. Loads are aligned 16-byte
+ * chunks, as in every packed-side reader here: they may cover up to 15 bytes before a stream's
+ * first and after its last byte, inside the 16-byte lines the stream itself touches.
+ * Parallelism: across streams, and inside each 4608-byte window of a stream. From message to
+ * message inside ONE stream the walk is serial: a message's start is only known from its
+ * predecessor's header and end. One stream of very many small messages is therefore walked by
+ * one wave, at about the cost of a window per message.
+ * d_workspace: caller-owned device memory, 256-B aligned, at least
+ * capnp_packed_split_workspace_bytes(n, 0) bytes, required for n > 0 (NULL, misaligned or
+ * short: INVALID_ARGUMENT). in_bytes_bound is the caller's upper bound on the sum of d_in_len
+ * (the lengths live on the device); it sizes the window tables that let a wave cross a window
+ * its current message neither ends nor runs out of bytes in by one lookup. The tables are an
+ * acceleration only: with a smaller workspace (down to in_bytes_bound 0), or past the table's
+ * limit of n / 8 + 32768 windows, streams whose windows do not fit are walked window by window
+ * and the results are the same. A kernel sets the workspace up on every call; the library
+ * keeps no state for this call and allocates nothing, so it is asynchronous on `stream` and
+ * capturable in a hipGraph. Two calls in flight must not share a workspace.
+ * n == 0 writes d_msg_first[0] = 0 and nothing else (no workspace needed). The return value
+ * reports argument and launch errors only.
+ * ------------------------------------------------------------------------ */
+#define CAPNP_PACKED_SPLIT_MAX_STREAM_BYTES (1ull << 40)
+size_t capnp_packed_split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound);
+int capnp_packed_split_streams(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                               uint32_t n, uint64_t max_msgs, uint64_t* d_msg_first /* n + 1 */,
+                               uint64_t* d_msg_off /* max_msgs */, uint64_t* d_msg_len /* max_msgs */,
+                               uint64_t* d_msg_framed /* max_msgs */,
+                               uint32_t* d_msg_stream /* max_msgs; may be NULL */, uint64_t* d_consumed /* n */,
+                               int32_t* d_status /* n */, void* d_workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* Message.init (message.zig:341-394) segment-table parse of n framed messages
  * d_in[d_in_off[i] .. + d_in_len[i]) (e.g. the output of a decode batch).

@@ -166,6 +166,23 @@ pub extern "capnp_packed" fn capnp_packed_encode_dense_batch(
     d_out_off: [*]u64, d_out_len: [*]u64, d_status: [*]i32,
     dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
 ) c_int;
+/// Dense streams of packed messages split into their messages: what repeated
+/// `Reader.readPackedMessage` calls on one reader consume, for n streams at once and without
+/// knowing where a message starts. `d_msg_first` has n + 1 entries (the whole messages before
+/// each stream, the total last); row k of the tables (`max_msgs` rows; more are counted, not
+/// written) is a message's offset in `d_in`, its packed and its framed length and its stream.
+/// `d_consumed` / `d_status` are per stream. `d_ws`:
+/// `capnp_packed_split_workspace_bytes(n, in_bytes_bound)` bytes of device memory (the bound
+/// sizes the window tables, an acceleration only), 256-B aligned, not shared between calls in
+/// flight. A stream of more than `split_max_stream_bytes` bytes gets INVALID_ARGUMENT.
+pub const split_max_stream_bytes: u64 = 1 << 40;
+pub extern "capnp_packed" fn capnp_packed_split_workspace_bytes(n: u32, in_bytes_bound: u64) usize;
+pub extern "capnp_packed" fn capnp_packed_split_streams(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32, max_msgs: u64,
+    d_msg_first: [*]u64, d_msg_off: ?[*]u64, d_msg_len: ?[*]u64, d_msg_framed: ?[*]u64,
+    d_msg_stream: ?[*]u32, d_consumed: [*]u64, d_status: [*]i32,
+    d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
+) c_int;
 pub extern "capnp_packed" fn capnp_packed_decode_batch_ws(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
     d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u64,
