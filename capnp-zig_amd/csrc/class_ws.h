@@ -1,5 +1,6 @@
-// class_ws.h — the class workspace `q` of a batch of n units, as plain arithmetic: no HIP, no
-// device pointers. Every batch encode, decode and decoded-size call classes its units into this
+// class_ws.h — the class workspace `q` of a batch of n units, as plain arithmetic: no HIP and no
+// device pointers, but for q_tiles (the reserved counter's accessor, which the tile, window and
+// splitter kernels share; compiled under hipcc only). Every batch encode, decode and decoded-size call classes its units into this
 // block (class_count / class_scan / class_scatter_kernel, packed_kernels.hip) and every later
 // kernel of the call reads it; the framer's spec block (capnp_packed_abi.cpp: SpecBlock) is the
 // head and the window table of the same layout. tests/host/class_ws_test.cpp pins every
@@ -136,6 +137,14 @@ CPK_HD inline uint32_t huge_slot(uint32_t n, uint32_t idx) { return kQHead + n -
 CPK_HD inline uint32_t long_list_slot(uint32_t n, uint32_t nh, uint32_t i) {
     return i < nh ? huge_slot(n, i) : long_slot(i - nh);
 }
+
+// ---- device accessors (HIP only) ----
+#ifdef __HIPCC__
+// tiles / windows reserved so far (u64)
+__device__ __forceinline__ unsigned long long* q_tiles(uint32_t* q) {
+    return reinterpret_cast<unsigned long long*>(q + kSlotReserved);
+}
+#endif
 
 // What a launcher passes to kernels that take a list or a counter instead of the workspace.
 struct ClassWs {

@@ -1,7 +1,8 @@
 // kernels/common.h
 // Wave / block constants, the ST_* statuses (capnp_packed.h's codes) and the internal kSt*
-// statuses that one pass leaves for the next. Included by every header under kernels/ that names
-// a status or a block size.
+// statuses that one pass leaves for the next, and the few limits that more than one path checks
+// (so that no path includes another for a constant). Included by every header under kernels/ that
+// names a status or a block size.
 // DESIGN.md §2 (execution model), §2.4 (the read-message statuses).
 #pragma once
 #include <stdint.h>
@@ -53,5 +54,16 @@ constexpr int32_t kStWords = 0x7FFF0005;     // read-message: the words decoder'
 constexpr uint64_t kRdWordsMax = 1024;       // read-message: framed words the words decoder takes
 // status of a long unit between its listing and its worker's result
 constexpr int32_t kStPending = CAPNP_PACKED_DEVICE_ERROR;
+
+// ---- limits more than one path checks --------------------------------------
+// the encoders of segment lists, Message.init and Message.validate
+constexpr uint32_t kMsgMaxSegs = 512;  // Message.max_segment_count (message.zig:310)
+// the class pass (unit_class) and the small-unit decoders
+constexpr uint64_t kSmDecP = 512;     // decode: small = at most 512 packed bytes ...
+constexpr uint64_t kSmDecCap = 8192;  // ... into a slot of at most 8 KiB
+// the index walk and the words decoder
+constexpr uint64_t kIxSizeMax = 1ull << 31;       // size-only walk: longer units use decode_size_lane_kernel
+// the tile table (encode), the window table (decode, framer) and the splitter's message table
+constexpr uint32_t kTileSkip = 0xFFFFFFFFu;  // a table entry of a unit that went to the serial list
 
 }  // namespace cpk

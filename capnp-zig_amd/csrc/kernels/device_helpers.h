@@ -1,7 +1,8 @@
 // kernels/device_helpers.h
-// The small device helpers every path shares: global / LDS loads, DPP wave scans,
-// the compact / expand selectors and their LUTs, partial 16-B stores, vmcnt_at_most. DESIGN.md
-// §2.2 (scans, selectors), §2.3 (ring loads).
+// The small device helpers every path shares: global / LDS loads, DPP wave scans, wave_reserve
+// (a shared counter's ranges, one atomic per wave), the compact / expand selectors and their LUTs,
+// partial 16-B stores, vmcnt_at_most. DESIGN.md §2.2 (scans, selectors), §2.3 (ring loads), §2.6
+// (wave_reserve).
 // Leans on:
 //   common.h             kWave
 #pragma once
@@ -167,6 +168,24 @@ __device__ __forceinline__ uint32_t next_break(bool has, uint32_t v, uint32_t la
 
 __device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t l) {
     return __builtin_amdgcn_readlane(v, l);
+}
+
+// Consecutive ranges of a shared counter for a wave's lanes (k each, 0: none), in lane order,
+// with ONE atomic per wave: ~10K long units each adding to the one counter serialised at its L2
+// channel while the small-unit kernel loaded the memory system (config C5: 0.21 ms).
+__device__ __forceinline__ uint64_t wave_reserve(unsigned long long* ctr, uint64_t k) {
+    const uint32_t lane = lane_id();
+    uint64_t incl = k;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t o = __shfl_up(incl, d, kWave);
+        if (lane >= (uint32_t)d) incl += o;
+    }
+    const uint64_t total = __shfl(incl, kWave - 1, kWave);
+    uint64_t b = 0;
+    if (lane == 0 && total != 0) b = atomicAdd(ctr, (unsigned long long)total);
+    b = __shfl(b, 0, kWave);
+    return b + incl - k;
 }
 
 // Zero-byte tag of a little-endian word: bit k set <=> byte k != 0

@@ -41,13 +41,21 @@
 //           (generate_kernel) and the offsets scan.
 //
 // Where things are. Under kernels/, each header compiling on its own (make check-headers):
-//   kernels/common.h          wave / block constants, the ST_* and kSt* statuses
-//   kernels/device_helpers.h  loads, DPP wave scans, selectors and LUTs, partial stores, vmcnt_*
-//   kernels/generate_scan.h   generate_kernel and the offsets scan
-//   kernels/side_launch.h     host only: StreamCtx / SideLaunch, the launch flags
-// In this file, in the order of their definitions (which is the object's function order, so
-// neither a section nor an include may move): the banner-marked sections of the encoders, the
-// decoders, the class pass, validate, read-message and the framer, then the launchers.
+//   kernels/common.h            wave / block constants, the ST_* and kSt* statuses, shared limits
+//   kernels/device_helpers.h    loads, DPP wave scans, wave_reserve, selectors and LUTs, partial
+//                               stores, vmcnt_*
+//   kernels/message_init.h      message_init_kernel
+//   kernels/decode_size_lane.h  decode_size_lane_kernel (the size pass's fallback)
+//   kernels/decode_wave.h       the window machinery (wv_*), decode_wave_kernel (the fallback)
+//   kernels/read_message.h      packed_header, read_header_kernel
+//   kernels/generate_scan.h     generate_kernel and the offsets scan
+//   kernels/side_launch.h       host only: StreamCtx / SideLaunch, the launch flags
+// The order contract. This file includes every header under kernels/ directly, exactly once
+// (tests/test_kernel_headers.py), each where its section was; a header's own includes only name
+// what it leans on and are no-ops by then. The sections still in this file and the includes
+// between them, in this order, are the object's function order, so neither a section nor an
+// include may move: the banner-marked sections of the encoders, the decoders, the class pass,
+// validate, the framer and the splitter, then the launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -653,8 +661,6 @@ __global__ __launch_bounds__(kBlock) void encode_tiled_kernel(const uint8_t* __r
     }
     }  // queued units
 }
-
-constexpr uint32_t kMsgMaxSegs = 512;  // Message.max_segment_count (message.zig:310)
 
 // ---------------------------------------------------------------------------
 // ENCODE, C++ dialect (CAPNP_PACKED_DIALECT_CXX): the bytes the C++ capnp
@@ -2084,530 +2090,13 @@ __global__ __launch_bounds__(kBlock) void encode_message_kernel(const uint64_t* 
     }
 }
 
-// ---------------------------------------------------------------------------
-// Message.init on device (message.zig:341-394): the segment table of each framed
-// message, lane per message. seg_off / seg_len get max_segs entries per message
-// (row i at i * max_segs; segments past max_segs are counted, not listed).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void message_init_kernel(const uint8_t* __restrict__ in,
-                                                              const uint64_t* __restrict__ in_off,
-                                                              const uint64_t* __restrict__ in_len, uint32_t n,
-                                                              uint32_t max_segs, uint32_t* __restrict__ seg_count,
-                                                              uint64_t* __restrict__ seg_off,
-                                                              uint64_t* __restrict__ seg_len,
-                                                              int32_t* __restrict__ status) {
-    const uint32_t msg = blockIdx.x * kBlock + threadIdx.x;
-    if (msg >= n) return;
-    const uint8_t* const d = in + in_off[msg];
-    const uint64_t len = in_len[msg];
-    auto u32at = [&](uint64_t o) {
-        return (uint32_t)d[o] | ((uint32_t)d[o + 1] << 8) | ((uint32_t)d[o + 2] << 16) | ((uint32_t)d[o + 3] << 24);
-    };
-    int32_t st = ST_OK;
-    uint64_t count = 0;
-    if (len < 4) {
-        st = ST_EOS;  // :343 readInt
-    } else {
-        const uint32_t m1 = u32at(0);
-        if (m1 == 0xFFFFFFFFu) st = ST_SEGCOUNT;  // :346
-        else if ((uint64_t)m1 + 1 > kMsgMaxSegs) st = ST_SEGLIMIT;  // :348
-        else {
-            count = (uint64_t)m1 + 1;
-            const uint64_t header = 4 * (1 + count + ((count & 1) ? 0 : 1));
-            if (header > len) st = ST_TRUNC;  // :353
-            uint64_t o = header;
-            for (uint64_t i = 0; st == ST_OK && i < count; ++i) {
-                const uint64_t end = o + 8ull * u32at(4 + 4 * i);
-                if (end > len) { st = ST_TRUNC; break; }  // :380
-                if (i < max_segs) {
-                    seg_off[(uint64_t)msg * max_segs + i] = o;
-                    seg_len[(uint64_t)msg * max_segs + i] = end - o;
-                }
-                o = end;
-            }
-        }
-    }
-    seg_count[msg] = st == ST_OK ? (uint32_t)count : 0u;
-    status[msg] = st;
-}
+}  // namespace cpk
 
-// ---------------------------------------------------------------------------
-// Decoded size, lane per unit: the size pass's fallback for units of kIxSizeMax (2 GiB) packed
-// bytes or more, which the size-only index walk declines (kStNeedFull; launch_decode)
-// ---------------------------------------------------------------------------
-// Each lane owns ONE unit and walks its record chain (tag -> record length) exactly once,
-// counting the words. The lane keeps a sliding window of its packed bytes in registers: a
-// 32-byte view (q0..q3) plus one 16-byte piece in flight (n0, n1).
+#include "kernels/message_init.h"
+#include "kernels/decode_size_lane.h"
+#include "kernels/decode_wave.h"
 
-// View helper takes the window by value so the selects stay register selects
-// (members selected through `this` were turned into an indexed alloca in LDS).
-__device__ __forceinline__ uint32_t view_byte(uint64_t q0, uint64_t q1, uint64_t q2, uint64_t q3, uint32_t o) {
-    uint64_t a = (o & 8) ? q1 : q0;  // o < 32
-    uint64_t b = (o & 8) ? q3 : q2;
-    uint64_t q = (o & 16) ? b : a;
-    return (uint32_t)(q >> (8 * (o & 7))) & 0xFFu;
-}
-__device__ __forceinline__ void load_piece(const uint8_t* base, uint32_t npieces, uint32_t idx, uint64_t& a,
-                                           uint64_t& b) {
-    if (idx < npieces) {
-        uint4 v = *reinterpret_cast<const uint4*>(base + 16 * (uint64_t)idx);
-        a = (uint64_t)v.x | ((uint64_t)v.y << 32);
-        b = (uint64_t)v.z | ((uint64_t)v.w << 32);
-    } else {
-        a = 0;
-        b = 0;
-    }
-}
-
-// out / out_off / out_cap are not read (the launcher passes the batch's arguments as they are).
-__global__ __launch_bounds__(kBlock) void decode_size_lane_kernel(const uint8_t* __restrict__ in,
-                                                                  const uint64_t* __restrict__ in_off,
-                                                                  const uint64_t* __restrict__ in_len,
-                                                                  uint32_t n, uint8_t* __restrict__ out,
-                                                                  const uint64_t* __restrict__ out_off,
-                                                                  const uint64_t* __restrict__ out_cap,
-                                                                  uint64_t* __restrict__ out_len,
-                                                                  int32_t* __restrict__ status) {
-    const uint32_t unit = blockIdx.x * kBlock + threadIdx.x;
-    if (unit >= n) return;
-    if (status[unit] != kStNeedFull) return;  // only the units decode_index_kernel<true> declined
-    const uint8_t* src = in + in_off[unit];
-    const uint64_t P = in_len[unit];
-    const uint32_t s = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15);
-    const uint64_t end64 = s + P;
-    const uint8_t* base = src - s;
-    const uint32_t npieces = (uint32_t)((end64 + 15) >> 4);
-    // window: q0..q3 = pieces wb/16, wb/16+1; n0,n1 = piece wb/16+2 (in flight)
-    uint64_t q0, q1, q2, q3, n0, n1;
-    uint32_t wb = 0;
-    load_piece(base, npieces, 0, q0, q1);
-    load_piece(base, npieces, 1, q2, q3);
-    load_piece(base, npieces, 2, n0, n1);
-    auto ensure = [&](uint32_t p) {
-        while (p - wb >= 16) {
-            q0 = q2; q1 = q3; q2 = n0; q3 = n1;
-            wb += 16;
-            load_piece(base, npieces, (wb >> 4) + 2, n0, n1);
-        }
-    };
-    uint64_t pos = s;
-    uint64_t wo = 0;
-    int32_t st = ST_OK;
-    while (pos < end64) {
-        ensure((uint32_t)pos);
-        const uint32_t o = (uint32_t)pos - wb;
-        const uint32_t t = view_byte(q0, q1, q2, q3, o);
-        if (t == 0x00) {  // message.zig:101-110
-            if (pos + 2 > end64) { st = ST_EOF; break; }
-            const uint32_t c = view_byte(q0, q1, q2, q3, o + 1);
-            for (uint32_t k = 0; k <= c; ++k) ++wo;
-            pos += 2;
-        } else if (t == 0xFF) {  // message.zig:112-128
-            if (pos + 10 > end64) { st = ST_EOF; break; }
-            const uint32_t c = view_byte(q0, q1, q2, q3, o + 9);
-            if (pos + 10 + 8ULL * c > end64) { st = ST_EOF; break; }
-            ++wo;
-            pos += 10;
-            for (uint32_t k = 0; k < c; ++k) {  // the window follows the run (as the decoders read it)
-                ensure((uint32_t)pos);
-                ++wo;
-                pos += 8;
-            }
-        } else {  // message.zig:131-141
-            const uint32_t k = __popc(t);
-            if (pos + 1 + k > end64) { st = ST_EOF; break; }
-            ++wo;
-            pos += 1 + k;
-        }
-    }
-    if (st != ST_OK) {
-        out_len[unit] = 0;
-        status[unit] = st;
-        return;
-    }
-    const uint64_t U = 8 * wo;
-    out_len[unit] = U;
-    status[unit] = ST_OK;
-}
-
-// ---------------------------------------------------------------------------
-// DECODE fallback, wave per unit (long units of the indexed decoder, marked units
-// of the read-message passes; profiles/r01_decode_experiments.md)
-// ---------------------------------------------------------------------------
-// One wave owns one unit. The unit's packed bytes are processed in windows of
-// up to kWvWin bytes (one window for units up to ~4.5 KiB packed), each staged
-// in the wave's LDS slice with coalesced 16-B loads. Lane j owns the chunk
-// [j*C, (j+1)*C) of the window and must find the true record chain through it
-// (tag -> record length -> next tag, message.zig:152-191), which is serial:
-//
-//   walk A   every lane walks its chunk from the chunk start (a guess),
-//            marking the tags it visits in a per-byte mark array (walk id 1);
-//   walk B   every lane walks from the exit of its left neighbour's walk A
-//            (the neighbour's guess of where the chain enters this chunk),
-//            stopping as soon as it reaches a marked tag: from there the
-//            chain is the marked walk's, so its exit is known (walk id 2);
-//   rounds   lane j is verified when its entry equals lane j-1's exit and
-//            lane j-1 is verified (lane 0 enters at 0, the window start is a
-//            tag). Every lane whose entry disagrees re-walks from its
-//            neighbour's exit, again stopping at the first marked tag. Each
-//            round verifies at least the first disagreeing lane, so this ends
-//            in <= 64 rounds; because chains from different entries couple
-//            within a few records, 0-2 rounds are typical.
-//   count    each lane sums the output words of its verified records; a wave
-//            scan gives every lane its output word offset;
-//   expand   each lane expands its records (v_perm_b32 scatter of the nonzero
-//            bytes) and stores the words; zero runs and literal runs longer
-//            than a few words are handed to the whole wave (coalesced).
-//
-// The window's exit (lane 63's verified exit) is the next window's start, so
-// any unit size works; LDS-resident chunks keep every chain step an LDS read.
-constexpr uint32_t kWvWaves = 4;                      // waves (units) per block
-constexpr uint32_t kWvBlock = kWvWaves * kWave;
-constexpr uint32_t kWvWin = 4608;                     // packed bytes per window (64 chunks x 72 B)
-constexpr uint32_t kWvPk = kWvWin + 64;               // + 15 B alignment slack + 16 B overshoot + read slack
-constexpr uint32_t kWvCmin = 32;                      // minimum chunk bytes per lane
-constexpr uint32_t kWvStageK = (kWvPk / 16 + 63) / 64;
-constexpr uint32_t kEOFX = 0xFFFFFFFFu;               // "the chain ran past the end of the input"
-constexpr uint32_t kWvExtLane = 3;                    // longer literal runs are listed by the whole wave
-constexpr uint32_t kWvList = 1024;                    // output words per expand pass (u16 list in the mark array)
-constexpr uint32_t kPosMask = 0x1FFFu;                // list code: window position (< 8192)
-constexpr uint32_t kLit = 0x2000u;                    // list code: literal word (identity selector)
-constexpr uint32_t kZero = 0x8000u;                   // list code: zero word
-constexpr uint32_t kZero2 = kZero | (kZero << 16);
-static_assert(kWvList * 2 <= kWvWin, "list aliases the mark array");
-static_assert(kWvWin + 16 + 2058 < 8192, "list codes hold window positions");
-constexpr uint32_t kWvSlack = 16;                     // plausible entry offset into a chunk (records are <= 9 B)
-
-__device__ __forceinline__ uint32_t wv_sel_exit(uint32_t m, uint32_t e1, uint32_t e2, uint32_t e3, uint32_t e4,
-                                                uint32_t e5, uint32_t e6, uint32_t e7) {
-    uint32_t r = e7;
-    r = (m == 6) ? e6 : r;
-    r = (m == 5) ? e5 : r;
-    r = (m == 4) ? e4 : r;
-    r = (m == 3) ? e3 : r;
-    r = (m == 2) ? e2 : r;
-    r = (m == 1) ? e1 : r;
-    return r;
-}
-
-// Walk the chain from window position r to the first tag position >= cend,
-// marking visited tags with id (id 0: no marks). Stops at a tag marked by an
-// earlier walk and reports its id in hit (the caller maps it to that walk's
-// exit). Returns kEOFX if a record runs past the input end (rem bytes).
-__device__ __forceinline__ uint32_t wv_len(uint32_t t, uint32_t c) {  // record length for tag t
-    const uint32_t zf = (t == 0u) | (t == 0xFFu);             // 00 -> 2, FF -> 10 + 8c, else 1 + popc
-    return 1u + __popc(t) + zf + ((t == 0xFFu) ? 8u * c : 0u);
-}
-
-__device__ __forceinline__ uint32_t wv_walk(const uint8_t* pk, uint8_t* mk, uint32_t sh, uint32_t rem, uint32_t r,
-                                            uint32_t cend, uint32_t id, uint32_t& hit) {
-    uint32_t h = 0;
-    bool go = r < cend;
-    while (go) {  // body is branch-free: one loop exit
-        uint32_t m = mk[r];
-        uint32_t t = pk[sh + r];
-        uint32_t c = pk[sh + r + 9];
-        asm volatile("" : "+v"(m), "+v"(t), "+v"(c));  // issue the three LDS reads together, one wait
-        const uint32_t len = wv_len(t, c);
-        const bool coupled = m != 0;
-        mk[r] = (uint8_t)(coupled ? m : id);  // unconditional: rewrites m where coupled or id == 0
-        h = m;
-        const uint32_t nr = (r + len > rem) ? kEOFX : r + len;
-        r = coupled ? r : nr;
-        go = !coupled && r < cend;
-    }
-    hit = h;
-    return r;
-}
-
-// A window of a unit's packed bytes staged in the wave's LDS slice: window byte r (unit
-// byte X + r) at pk[sh + r] for r < nload. Records starting in [0, Pw) belong to the
-// window; nload adds the <= 9 bytes such a record reaches past Pw.
-struct WvWin {
-    const uint8_t* g;  // unit byte X
-    uint32_t sh;       // g & 15
-    uint32_t rem;      // unit bytes from X on (clamped to 2^31 - 1)
-    uint32_t Pw;       // window bytes
-    uint32_t nload;    // staged bytes
-};
-
-// Stage window [X, X + kWvWin) of a unit of P packed bytes and clear its marks.
-__device__ __forceinline__ WvWin wv_stage(uint8_t* pk, uint8_t* mk, const uint8_t* src, uint64_t P, uint64_t X,
-                                          uint32_t lane) {
-    WvWin w;
-    const uint64_t rem64 = P - X;
-    w.rem = rem64 > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)rem64;
-    w.Pw = min(w.rem, kWvWin);
-    w.nload = min(w.rem, w.Pw + 16);
-    w.g = src + X;
-    w.sh = (uint32_t)(reinterpret_cast<uintptr_t>(w.g) & 15);
-    wave_lds_sync();
-    stage_linear<kWvStageK>(pk, w.g - w.sh, (w.sh + w.nload + 15) >> 4, lane);
-    for (uint32_t i = lane * 16; i < w.Pw; i += 16 * kWave) *reinterpret_cast<uint4*>(mk + i) = make_uint4(0, 0, 0, 0);
-    wave_lds_sync();
-    return w;
-}
-
-// The record chain through a staged window whose first record starts at window byte d0
-// (lane 0's entry, exact). Lane j owns the chunk [cs, ce); on return `ent` is the verified
-// record start where the chain enters it, and the result is the window's exit: the first
-// record start at or past Pw (window-relative), or kEOFX when a record runs past the
-// unit's end (walks A and B and the verification rounds: see above).
-__device__ __forceinline__ uint32_t wv_resolve(const uint8_t* pk, uint8_t* mk, const WvWin& w, uint32_t d0,
-                                               uint32_t lane, uint32_t& ent, uint32_t& cs, uint32_t& ce) {
-    const uint32_t C = max(kWvCmin, (w.Pw + 63) >> 6);
-    cs = min(lane * C, w.Pw);
-    ce = min(cs + C, w.Pw);
-
-    // ---- walk A: lane 0 from d0, every other lane from its chunk start (a guess) -----
-    const uint32_t a0 = lane == 0 ? d0 : cs;
-    uint32_t hit;
-    const uint32_t e1 = wv_walk(pk, mk, w.sh, w.rem, a0, ce, 1, hit);
-    uint32_t e2 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0, e7 = 0;
-
-    // ---- walk B: enter where the left neighbour's walk A left off ---------------------
-    // An entry far past the chunk start (a misread FF run, or a misread record running
-    // past the input end) would only pass through; keep walk A's guess.
-    ent = __shfl_up(e1, 1, kWave);
-    if (lane == 0) ent = d0;
-    else if (ent > cs + kWvSlack) ent = cs;
-    uint32_t ex = e1;
-    if (ent != a0) {
-        ex = wv_walk(pk, mk, w.sh, w.rem, ent, ce, 2, hit);
-        if (hit) ex = wv_sel_exit(hit, e1, e2, e3, e4, e5, e6, e7);
-        e2 = ex;
-    }
-
-    // ---- verification rounds ------------------------------------------------------------
-    // Lanes before the first disagreeing lane f are verified. A disagreeing lane re-walks
-    // from its neighbour's exit when that neighbour is verified (lane f), or when the
-    // neighbour agrees with ITS neighbour this round and the exit is a plausible entry
-    // (<= kWvSlack into the chunk): far or EOF exits adopted from an unverified neighbour
-    // would otherwise ripple one lane per round.
-    uint32_t nid = 3;
-    for (;;) {
-        uint32_t prev = __shfl_up(ex, 1, kWave);
-        if (lane == 0) prev = d0;
-        const bool bad = ent != prev;
-        const uint64_t bm = __ballot(bad);
-        if (!bm) break;
-        const uint32_t f = (uint32_t)__builtin_ctzll(bm);
-        const bool left_bad = lane > 0 && ((bm >> (lane - 1)) & 1);
-        if (bad && (lane == f || (!left_bad && prev <= cs + kWvSlack))) {
-            ent = prev;
-            const uint32_t id = nid <= 7 ? nid : 0;
-            ex = wv_walk(pk, mk, w.sh, w.rem, ent, ce, id, hit);
-            if (hit) ex = wv_sel_exit(hit, e1, e2, e3, e4, e5, e6, e7);
-            e3 = (id == 3) ? ex : e3;
-            e4 = (id == 4) ? ex : e4;
-            e5 = (id == 5) ? ex : e5;
-            e6 = (id == 6) ? ex : e6;
-            e7 = (id == 7) ? ex : e7;
-            ++nid;
-        }
-    }
-    return readlane(ex, kWave - 1);
-}
-
-// Output words of a lane's verified records [ent, ce).
-__device__ __forceinline__ uint32_t wv_count(const uint8_t* pk, uint32_t sh, uint32_t ent, uint32_t ce) {
-    uint32_t words = 0;
-    for (uint32_t r = ent; r < ce;) {
-        uint32_t t = pk[sh + r];
-        uint32_t b1 = pk[sh + r + 1];
-        uint32_t c9 = pk[sh + r + 9];
-        asm volatile("" : "+v"(t), "+v"(b1), "+v"(c9));
-        words += 1u + ((t == 0u) ? b1 : 0u) + ((t == 0xFFu) ? c9 : 0u);
-        r += wv_len(t, c9);
-    }
-    return words;
-}
-
-// Expand the window's verified records into o[0 .. total): lane records produce words
-// [wbeg, wend). Passes of kWvList output words:
-//   list:   each lane walks its verified records once more and writes, for every output
-//           word of the pass that its records produce, a 16-bit source code into a list
-//           in LDS (the mark array, dead by now): code = q (window position of a tag;
-//           word = perm(bytes q+1..q+8, lut[byte q])) or kLit | (s - 1) (literal word at
-//           bytes s..s+7); zero-run words keep the kZero code the list is reset to;
-//   expand: lane i turns list entry i into its word and stores it, so every store
-//           instruction writes 64 consecutive output words (512 B).
-__device__ __forceinline__ void wv_expand(const uint8_t* pk, uint8_t* mk, const uint64_t* lut, const WvWin& w,
-                                          uint32_t ent, uint32_t ce, uint32_t wbeg, uint32_t wend, uint32_t total,
-                                          uint64_t* o, uint32_t lane) {
-    const uint32_t sh = w.sh;
-    uint16_t* const list = reinterpret_cast<uint16_t*>(mk);
-    for (uint32_t W0 = 0; W0 < total; W0 += kWvList) {
-        const uint32_t W1 = min(total, W0 + kWvList);
-        wave_lds_sync();
-        for (uint32_t i = lane * 8; i < kWvList; i += 8 * kWave)
-            *reinterpret_cast<uint4*>(list + i) = make_uint4(kZero2, kZero2, kZero2, kZero2);
-        wave_lds_sync();
-        uint32_t pn = 0, ps = 0, pw = 0;  // long literal run handed to the wave
-        if (wbeg < W1 && wend > W0) {
-            uint32_t wo = wbeg;
-            for (uint32_t r = ent; r < ce && wo < W1;) {
-                uint32_t t = pk[sh + r];
-                uint32_t b1 = pk[sh + r + 1];
-                uint32_t c9 = pk[sh + r + 9];
-                asm volatile("" : "+v"(t), "+v"(b1), "+v"(c9));
-                const bool z = t == 0, f = t == 0xFFu;
-                if (!z && wo >= W0) list[wo - W0] = (uint16_t)r;
-                if (f && c9) {  // literal words r+10 .. r+10+8c
-                    if (c9 <= kWvExtLane || pn != 0) {  // one long run per lane goes to the wave
-                        for (uint32_t i = 0; i < c9; ++i) {
-                            const uint32_t wi = wo + 1 + i;
-                            if (wi >= W0 && wi < W1) list[wi - W0] = (uint16_t)(kLit | (r + 9 + 8 * i));
-                        }
-                    } else {
-                        pn = c9;
-                        ps = r + 9;
-                        pw = wo + 1;
-                    }
-                }
-                wo += 1u + (z ? b1 : 0u) + (f ? c9 : 0u);
-                r += wv_len(t, c9);
-            }
-        }
-        uint64_t pm = __ballot(pn != 0);
-        while (pm) {  // long literal runs: the whole wave fills their entries
-            const uint32_t l = (uint32_t)__builtin_ctzll(pm);
-            pm &= pm - 1;
-            const uint32_t nn = readlane(pn, l), ss = readlane(ps, l), ww = readlane(pw, l);
-            for (uint32_t i = lane; i < nn; i += kWave) {
-                const uint32_t wi = ww + i;
-                if (wi >= W0 && wi < W1) list[wi - W0] = (uint16_t)(kLit | (ss + 8 * i));
-            }
-        }
-        wave_lds_sync();
-        for (uint32_t i = W0 + lane; i < W1; i += kWave) {
-            const uint32_t code = list[i - W0];
-            const uint32_t q = code & kPosMask;
-            const bool lit = (code & kLit) != 0;
-            uint64_t word = 0;
-            if (!(code & kZero)) {
-                if (!lit || q + 9 <= w.nload) {  // a tag's bytes are always staged
-                    const uint32_t t = lit ? 0xFFu : pk[sh + q];
-                    word = perm64(lds_u64_at(pk, sh + q + 1), lut[t]);
-                } else {  // literal word past the staged bytes (long FF run), inside the input
-                    word = ld_u64(w.g + q + 1);
-                }
-            }
-            __builtin_nontemporal_store(word, o + i);  // streaming output (as the fill pass)
-        }
-    }
-}
-
-// SEL: kWvMarked the units a first pass marked kStNeedFull (the read-message passes, the words
-// decoder's units stopped at their capacity; q, when given, counts them: 0 returns at once);
-// kWvLong the long units the window table could not hold (the serial list that
-// long_windows_kernel fills), one after another.
-constexpr int kWvMarked = 1, kWvLong = 2;
-
-template <int SEL>
-__global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __restrict__ in,
-                                                               const uint64_t* __restrict__ in_off,
-                                                               const uint64_t* __restrict__ in_len, uint32_t n,
-                                                               uint8_t* __restrict__ out,
-                                                               const uint64_t* __restrict__ out_off,
-                                                               const uint64_t* __restrict__ out_cap,
-                                                               uint64_t* __restrict__ out_len,
-                                                               int32_t* __restrict__ status, uint32_t* q) {
-    __shared__ __attribute__((aligned(16))) uint8_t pk_all[kWvWaves * kWvPk];
-    __shared__ __attribute__((aligned(16))) uint8_t mk_all[kWvWaves * kWvWin];
-    __shared__ uint64_t lut[256];  // tag -> v_perm selector that scatters the packed bytes (FF: identity, 00: zero)
-    constexpr bool CK = SEL == kWvMarked;
-    if (CK && q && *q == 0) return;  // kWvMarked with a count of marked units: none
-    const bool QD = SEL == kWvLong;
-    if (QD && q[kSlotSerial] == 0) return;  // no serial units (block-uniform)
-    lut[threadIdx.x] = expand_selector(threadIdx.x);
-    __syncthreads();
-    const uint32_t lane = lane_id();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint8_t* pk = pk_all + wave * kWvPk;
-    uint8_t* mk = mk_all + wave * kWvWin;
-    // CK: a first pass ran; this kernel takes only the units it marked kStNeedFull, with a
-    // small grid striding over the batch (64 statuses per load). QD: the serial list, a
-    // wave per entry striding over it (no shared atomic cursor: contended takes serialise).
-    const uint32_t* const serial = q + serial_off(n);
-    const uint32_t nq = QD ? q[kSlotSerial] : n;
-    const uint32_t stride = QD ? gridDim.x * kWvWaves : gridDim.x * kWvWaves * kWave;
-    for (uint32_t ubase = QD ? blockIdx.x * kWvWaves + wave : (blockIdx.x * kWvWaves + wave) * kWave; ubase < nq;
-         ubase += stride) {
-    uint64_t todo = 1;
-    if (CK) {
-        const uint32_t u = ubase + lane;
-        todo = __ballot(u < n && status[u] == kStNeedFull);
-    }
-    while (todo) {  // wave-uniform
-    const uint32_t unit = CK ? ubase + (uint32_t)__builtin_ctzll(todo) : __builtin_amdgcn_readfirstlane(serial[ubase]);
-    todo &= todo - 1;
-    const uint8_t* src = in + in_off[unit];
-    const uint64_t P = in_len[unit];
-    uint8_t* dstb = out + out_off[unit];
-    const uint64_t capw = out_cap[unit] >> 3;
-    if (reinterpret_cast<uintptr_t>(dstb) & 7) {
-        if (lane == 0) {
-            out_len[unit] = 0;
-            status[unit] = ST_ARG;
-        }
-        continue;
-    }
-    uint64_t* const dst = reinterpret_cast<uint64_t*>(dstb);
-
-    uint64_t X = 0;   // packed position of the current window (always a tag)
-    uint64_t Wb = 0;  // output words before the current window
-    int32_t st = ST_OK;
-    bool fits = true;
-    if (QD) {
-        // a counting walk first (the serial units are the rare ones the window table
-        // cannot hold): a truncated or oversized unit writes nothing, as unpackPacked
-        // returns its error before any output (message.zig:88-145)
-        while (X < P) {
-            const WvWin w = wv_stage(pk, mk, src, P, X, lane);
-            uint32_t ent, cs, ce;
-            const uint32_t xw = wv_resolve(pk, mk, w, 0, lane, ent, cs, ce);
-            if (xw == kEOFX) {
-                st = ST_EOF;
-                break;
-            }
-            const uint32_t words = wv_count(pk, w.sh, ent, ce);
-            Wb += readlane(wave_incl_sum(words), kWave - 1);
-            X += xw;
-        }
-        if (st != ST_OK || Wb > capw) {
-            if (lane == 0) {
-                out_len[unit] = st == ST_OK ? 8 * Wb : 0;
-                status[unit] = st != ST_OK ? st : ST_SPACE;
-            }
-            continue;
-        }
-        X = 0;
-        Wb = 0;
-    }
-    while (X < P) {
-        const WvWin w = wv_stage(pk, mk, src, P, X, lane);
-        uint32_t ent, cs, ce;
-        const uint32_t xw = wv_resolve(pk, mk, w, 0, lane, ent, cs, ce);
-        if (xw == kEOFX) {
-            st = ST_EOF;
-            break;
-        }
-        const uint32_t words = wv_count(pk, w.sh, ent, ce);
-        const uint32_t incl = wave_incl_sum(words);
-        const uint32_t total = readlane(incl, kWave - 1);
-        if (Wb + total > capw) fits = false;
-        if (fits) wv_expand(pk, mk, lut, w, ent, ce, incl - words, incl, total, dst + Wb, lane);
-        Wb += total;
-        X += xw;
-    }
-    if (lane == 0) {
-        out_len[unit] = (st == ST_OK) ? 8 * Wb : 0;
-        status[unit] = (st != ST_OK) ? st : (fits ? ST_OK : ST_SPACE);
-    }
-    }  // marked units
-    }  // unit loop
-}
+namespace cpk {
 
 // ---------------------------------------------------------------------------
 // DECODE, indexed two-pass decoder (the default)
@@ -2633,7 +2122,6 @@ __global__ __launch_bounds__(kWvBlock) void decode_wave_kernel(const uint8_t* __
 // front of the slot (rec = nullptr).
 constexpr uint32_t kIxDead = 0xFFFFFFFFu;         // walk position of a lane with nothing (more) to walk
 constexpr uint32_t kFlPieces = 320;               // pass-2 window: 64 lanes x 5 pieces
-constexpr uint64_t kIxSizeMax = 1ull << 31;       // size-only walk: longer units use decode_size_lane_kernel
 // record bytes per unit: 64 B per 8 rounds (+1 store) of at most kFlPieces * 16 B
 constexpr uint32_t kRecStride = 64 * ((kFlPieces * 16 / 64 + 8) / 8);
 static_assert(kRecStride == kRecBytes, "record region stride (class_ws.h)");
@@ -3626,8 +3114,6 @@ __global__ __launch_bounds__(kLwWaves * kWave) void decode_words_kernel(
 enum : uint32_t { CL_LONG = 0, CL_HUGE = 1, CL_SMALL = 2, CL_MID = 3 };  // + bins 0 .. CL_MID_BINS - 1
 constexpr uint32_t kEsBinsQ = 4;  // encode's small-unit bins (mid-list bins 4 .. 7, kEsBins)
 constexpr uint64_t kSmEncWords = 64;  // encode: units of at most 64 words are small
-constexpr uint64_t kSmDecP = 512;     // decode: small = at most 512 packed bytes ...
-constexpr uint64_t kSmDecCap = 8192;  // ... into a slot of at most 8 KiB
 constexpr uint64_t kMidSplitP = 1280; // decode: mid units of at most this many packed bytes (bins 0 .. 2)
 constexpr uint64_t kWordsCapMax = 8192;  // decode: the words decoder takes slots of at most 8 KiB
 
@@ -3874,7 +3360,6 @@ __global__ __launch_bounds__(kClassBlock) void class_scatter_kernel(const uint8_
 //                      written there; the unit's last tile writes out_len and status.
 // The table lives in the class workspace after the class lists (class_ws.h): tile sizes
 // (u64), units, first tile of the unit; capacity tile_cap(n) tiles.
-constexpr uint32_t kTileSkip = 0xFFFFFFFFu;  // a table entry of a unit that went to the serial list
 struct TileTab {
     uint64_t* size;
     uint32_t* unit;
@@ -3894,28 +3379,6 @@ __device__ __forceinline__ TileTab tile_tab(uint32_t* q, uint32_t n) {
     t.unit = q + tile_tab_off(n) + tile_unit_col(t.cap);
     t.first = t.unit + t.cap;
     return t;
-}
-// tiles / windows reserved so far (u64)
-__device__ __forceinline__ unsigned long long* q_tiles(uint32_t* q) {
-    return reinterpret_cast<unsigned long long*>(q + kSlotReserved);
-}
-
-// Consecutive ranges of a shared counter for a wave's lanes (k each, 0: none), in lane order,
-// with ONE atomic per wave: ~10K long units each adding to the one counter serialised at its L2
-// channel while the small-unit kernel loaded the memory system (config C5: 0.21 ms).
-__device__ __forceinline__ uint64_t wave_reserve(unsigned long long* ctr, uint64_t k) {
-    const uint32_t lane = lane_id();
-    uint64_t incl = k;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t o = __shfl_up(incl, d, kWave);
-        if (lane >= (uint32_t)d) incl += o;
-    }
-    const uint64_t total = __shfl(incl, kWave - 1, kWave);
-    uint64_t b = 0;
-    if (lane == 0 && total != 0) b = atomicAdd(ctr, (unsigned long long)total);
-    b = __shfl(b, 0, kWave);
-    return b + incl - k;
 }
 
 __global__ __launch_bounds__(256) void long_tiles_kernel(const uint64_t* __restrict__ in_len, uint32_t n, uint32_t* q) {
@@ -5498,105 +4961,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 4))) v
     }
 }
 
-// ---------------------------------------------------------------------------
-// Reader.readPackedMessage, batched (reader.zig:84-156)
-// ---------------------------------------------------------------------------
-// Unit i is one reader's buffered packed stream; one message is decoded from its
-// front (launch_read_message):
-//   1. read_header_kernel: lane per unit, decodes records until the segment table
-//      is complete (one record for a 1-segment message) and writes the framed
-//      length to out_len, or the header error to status;
-//      (ROUTE: messages of at most kRdWordsMax framed words kStWords, longer ones kStNeedWalk);
-//   2. messages of more than kRdWordsMax words: decode_index_kernel<true, kRdWalk> (the walk
-//      alone, consumed) and decode_index_kernel<false, kRdGate> (the records over in_len =
-//      consumed), then the fill pass and the full-path fallback over in_len = consumed;
-//   3. the others: decode_words_kernel<true> (round 6), which stops each lane's walk at the
-//      first record boundary that reaches the framed length and applies the reader's
-//      overshoot / end-of-stream rules there; consumed = the bytes it walked.
-constexpr uint64_t kMaxTotalWords = 8ull * 1024 * 1024;  // reader.zig:6
-constexpr uint64_t kMaxSegments = 512;                   // message.zig:310
-constexpr uint64_t kHdrMaxWords = 257;                   // (1 + 512 + pad) u32 = 257 words
+}  // namespace cpk
 
-// Pass 1. Checks follow the reference's order: a record cut short by the end of
-// the stream (EndOfStream), then after the first record InvalidSegmentCount /
-// SegmentCountLimitExceeded (reader.zig:121-125), then once header_bytes are
-// decoded MessageTooLarge (:140). Segment sizes are summed from the header's
-// words as the records produce them (zero words add nothing). packed_header returns the
-// status and, when OK, the framed length in `needed`.
-__device__ int32_t packed_header(const uint8_t* __restrict__ p, uint64_t P, uint64_t& needed) {
-    uint64_t r = 0;          // read cursor
-    uint64_t words = 0;      // decoded words (out.items.len / 8)
-    uint64_t count = 0;      // segment count (set by word 0)
-    uint32_t count_m1 = 0;
-    uint64_t total = 0;      // sum of the sizes decoded so far
-    needed = 0;
-    for (;;) {
-        if (r >= P) return ST_EOS;  // :95 readByte
-        const uint32_t t = p[r++];
-        uint64_t w0 = 0;
-        uint32_t c = 0;
-        const uint8_t* lit = p;
-        if (t == 0x00) {  // :96-99
-            if (r >= P) return ST_EOS;
-            c = p[r++];
-        } else if (t == 0xFF) {  // :100-110
-            if (P - r < 9) return ST_EOS;
-            w0 = ld_u64(p + r);
-            c = p[r + 8];
-            r += 9;
-            if (P - r < 8ull * c) return ST_EOS;
-            lit = p + r;
-            r += 8ull * c;
-        } else {  // :111-119
-            if (P - r < (uint64_t)__popc(t)) return ST_EOS;
-            for (uint32_t k = 0; k < 8; ++k)
-                if ((t >> k) & 1u) w0 |= (uint64_t)p[r++] << (8 * k);
-        }
-        // the record's words that hold header u32s: u32 j of the frame is
-        // segment count - 1 (j = 0) or the size of segment j - 1 (1 <= j <= count)
-        const uint64_t nw = 1ull + c;
-        if (words == 0) {
-            count_m1 = (uint32_t)w0;
-            count = (uint64_t)count_m1 + 1;
-        }
-        if (t != 0x00) {
-            for (uint64_t i = 0; i < nw && words + i < kHdrMaxWords; ++i) {
-                const uint64_t w = i == 0 ? w0 : ld_u64(lit + 8 * (i - 1));
-                const uint64_t j = 2 * (words + i);
-                if (j >= 1 && j <= count) total += (uint32_t)w;
-                if (j + 1 <= count) total += w >> 32;
-            }
-        }
-        words += nw;
-        // :121-144 (out.items.len >= 4 after any record)
-        if (count_m1 == 0xFFFFFFFFu) return ST_SEGCOUNT;
-        if (count > kMaxSegments) return ST_SEGLIMIT;
-        const uint64_t header_bytes = 4 * (1 + count + ((count & 1) ? 0 : 1));
-        if (8 * words >= header_bytes) {
-            if (total > kMaxTotalWords) return ST_TOOLARGE;
-            needed = header_bytes + 8 * total;
-            return ST_OK;
-        }
-    }
-}
+#include "kernels/read_message.h"
 
-// ROUTE (launch_read_message): a message of at most kRdWordsMax framed words goes to the words
-// decoder (kStWords), a longer one to the walk passes (kStNeedWalk); errors stand.
-template <bool ROUTE>
-__global__ __launch_bounds__(kBlock) void read_header_kernel(const uint8_t* __restrict__ in,
-                                                             const uint64_t* __restrict__ in_off,
-                                                             const uint64_t* __restrict__ in_len, uint32_t n,
-                                                             uint64_t* __restrict__ out_len,
-                                                             uint64_t* __restrict__ consumed,
-                                                             int32_t* __restrict__ status) {
-    const uint32_t unit = blockIdx.x * kBlock + threadIdx.x;
-    if (unit >= n) return;
-    uint64_t needed = 0;
-    const int32_t st = packed_header(in + in_off[unit], in_len[unit], needed);
-    status[unit] = (ROUTE && st == ST_OK) ? ((needed >> 3) <= kRdWordsMax ? kStWords : kStNeedWalk) : st;
-    out_len[unit] = st == ST_OK ? needed : 0;
-    consumed[unit] = 0;
-}
+namespace cpk {
 
 // ---------------------------------------------------------------------------
 // Resumable framing of packed socket streams (capnp_packed_framer_*).

@@ -28,7 +28,7 @@ ABI = {rs.END_OF_STREAM: 8, rs.INVALID_SEGMENT_COUNT: 9, rs.SEGMENT_COUNT_LIMIT_
 ABI_END_OF_STREAM = ABI[rs.END_OF_STREAM]
 ORACLE_TO_ABI = {0: ABI_OK, -1: 8, -2: 9, -3: 10, -6: 11, -7: 12}
 
-# The walk's window: kWvWin of csrc/packed_kernels.hip (64 chunks of 72 packed bytes), which the
+# The walk's window: kWvWin of csrc/kernels/decode_wave.h (64 chunks of 72 packed bytes), which the
 # library reports as cpk::framer_window_bytes() and framer_read_locked compares spans with.
 W = 4608
 HEADERLESS_TABLE_WINDOWS = 64  # framer_read_locked: header not decoded, held bytes over 64 windows

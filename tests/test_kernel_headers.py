@@ -1,9 +1,15 @@
 """Every kernel header (capnp-zig_amd/csrc/kernels/*.h) compiles on its own: it includes what it
 uses, so the dependencies each header names in its opening comment are the ones the compiler
 sees. Runs the Makefile's check-headers command (hipcc -fsyntax-only for gfx950, no GPU needed)
-on one header per case."""
+on one header per case.
+
+The order contract, from the text alone: packed_kernels.hip includes every header of that
+directory directly, exactly once, so the order of functions in the object is read from that one
+file and no header enters the translation unit only through another header."""
+import collections
 import glob
 import os
+import re
 import shutil
 import subprocess
 
@@ -17,6 +23,13 @@ HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(PKG, "csrc"
 
 def test_headers_found():
     assert HEADERS, "no header under capnp-zig_amd/csrc/kernels/"
+
+
+def test_kernel_file_includes_every_header_once():
+    with open(os.path.join(PKG, "csrc", "packed_kernels.hip")) as f:
+        included = collections.Counter(re.findall(r'^\s*#\s*include\s+"kernels/([^"/]+\.h)"', f.read(), re.M))
+    assert set(included) == set(HEADERS), sorted(set(included) ^ set(HEADERS))
+    assert all(n == 1 for n in included.values()), {h: n for h, n in included.items() if n != 1}
 
 
 @pytest.mark.parametrize("header", HEADERS)
