@@ -184,6 +184,13 @@ SIGNATURES = {
     "capnp_packed_encode_dense_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64,
                                                        ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _sz,
                                                        _vp]),
+    "capnp_packed_encode_framed": (ctypes.c_int, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_uint32]),
+    "capnp_packed_encode_framed_workspace_bytes": (_sz, [ctypes.c_uint32]),
+    "capnp_packed_encode_framed_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                                        ctypes.c_uint32, _vp, _sz, _vp]),
+    "capnp_packed_encode_framed_dense_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64,
+                                                              ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                              _sz, _vp]),
     "capnp_packed_split_workspace_bytes": (_sz, [ctypes.c_uint32, ctypes.c_uint64]),
     "capnp_packed_split_streams": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -311,6 +318,21 @@ def pack_packed(data, dialect="zig") -> bytes:
     else:
         st = lib().capnp_packed_encode_dialect(_cbuf(data), len(data), out, cap, ctypes.byref(n), d)
     _raise(st, "packPacked")
+    return out.raw[:n.value]
+
+
+def pack_message(framed, dialect="zig") -> bytes:
+    """One framed message (toBytes' bytes) packed (capnp_packed_encode_framed). dialect="cxx":
+    the segment table and each segment as pieces of their own, the bytes of capnp convert
+    binary:packed and pycapnp; "zig": packPacked(framed). The message must be exactly its table
+    plus its segments (TruncatedMessage and the table errors; InvalidArgument for trailing words)."""
+    d = _dialect(dialect)
+    framed = bytes(framed)
+    cap = encode_bound(len(framed) - len(framed) % 8)
+    out = ctypes.create_string_buffer(max(1, cap))
+    n = _sz()
+    st = lib().capnp_packed_encode_framed(_cbuf(framed), len(framed), out, cap, ctypes.byref(n), d)
+    _raise(st, "packMessage")
     return out.raw[:n.value]
 
 
@@ -1009,6 +1031,83 @@ def encode_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, ba
     _raise(lib().capnp_packed_encode_dense_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base, cap,
                                                  _ptr(out_off), _ptr(out_len), _ptr(status), d, *_ws(ws),
                                                  _stream(stream)), "encode_dense_batch")
+
+
+def framed_workspace(n_units: int, device="cuda"):
+    """Device workspace of encode_framed_batch (capnp_packed_encode_framed_workspace_bytes). Two
+    calls in flight must not share one."""
+    nbytes = lib().capnp_packed_encode_framed_workspace_bytes(n_units)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def encode_framed_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status, stream=None, ws=None,
+                        dialect="zig") -> None:
+    """encode_batch over framed messages (capnp_packed_encode_framed_batch): every unit is checked
+    as one whole framed message (the table errors, TRUNCATED_MESSAGE, INVALID_ARGUMENT for trailing
+    words; a failed unit's slot stays untouched), and dialect="cxx" packs its segment table and
+    each segment as pieces of their own. d_out=None: sizes only. ws: a framed_workspace() tensor
+    (None: one is allocated for the call)."""
+    d = _dialect(dialect)
+    n = _units(in_off, in_len, out_len, status)
+    if d_out is not None:
+        _units(in_off, out_off, out_cap)
+    if ws is None and n:
+        ws = framed_workspace(n, device=in_off.device)
+    _raise(lib().capnp_packed_encode_framed_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out),
+                                                  _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), d,
+                                                  *_ws(ws), _stream(stream)), "encode_framed_batch")
+
+
+def encode_framed_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, base=0, cap=None, stream=None,
+                              ws=None, dialect="zig") -> None:
+    """encode_dense_batch over framed messages (capnp_packed_encode_framed_dense_batch): the batch
+    form of writing message after message to one packed stream; with dialect="cxx" the stream is
+    byte for byte what capnp convert binary:packed writes. A failed unit takes no bytes. ws: a
+    dense_workspace() tensor (None: one is allocated for the call)."""
+    d = _dialect(dialect)
+    n = _units(in_off, in_len, out_len, status)
+    if out_off is not None and out_off.numel() < n + 1:
+        raise InvalidArgument(f"out_off has {out_off.numel()} entries for {n} units (n + 1 needed)")
+    if cap is None:
+        cap = 0 if d_out is None else d_out.numel()
+    if ws is None and n:
+        ws = dense_workspace(n, device=in_off.device)
+    _raise(lib().capnp_packed_encode_framed_dense_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base,
+                                                        cap, _ptr(out_off), _ptr(out_len), _ptr(status), d, *_ws(ws),
+                                                        _stream(stream)), "encode_framed_dense_batch")
+
+
+def write_packed_messages(frames, dialect="zig", device="cuda") -> bytes:
+    """The packed stream of a list of framed messages, the writer's half of read_packed_messages:
+    one upload of the frames end to end, one encode_framed_dense_batch, one download of the
+    stream. Raises the first failed frame's error, with that frame's index."""
+    _dialect(dialect)
+    frames = [bytes(f) for f in frames]
+    if not frames:
+        return b""
+    dev = torch.device(device)
+    n = len(frames)
+    # every frame starts on a word: a frame whose length is no multiple of 8 (its own error)
+    # must not misalign the next
+    lens = np.array([len(f) for f in frames], dtype=np.int64)
+    starts = np.concatenate(([0], np.cumsum((lens + 7) & ~7)[:-1])).astype(np.int64)
+    host = np.zeros(int(((lens + 7) & ~7).sum()) + 16, dtype=np.uint8)
+    for s, f in zip(starts.tolist(), frames):
+        host[s:s + len(f)] = np.frombuffer(f, dtype=np.uint8)
+    d_in = torch.from_numpy(host).to(dev)
+    in_off = torch.from_numpy(starts).to(dev)
+    in_len = torch.from_numpy(lens).to(dev)
+    cap = encode_bound(int(host.size))
+    d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    encode_framed_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, cap=cap, dialect=dialect)
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st != OK)
+    if bad.size:
+        _raise(int(st[bad[0]]), f"write_packed_messages: frame {int(bad[0])}")
+    return d_out[:int(out_off[n].item())].cpu().numpy().tobytes()
 
 
 def encoded_size_batch(d_in, in_off, in_len, out_len, status, stream=None, dialect="zig") -> None:

@@ -311,7 +311,7 @@ uint64_t unpack_bound(size_t n) { return n > (UINT64_MAX / 1024) ? UINT64_MAX : 
 constexpr size_t kFastDecodeMax = 24 * 1024;  // packed bytes (the serial window walk passes the batch path near 32 KB)
 constexpr size_t kFastEncodeMax = 4096;       // unpacked bytes: one 512-word tile
 
-enum class Single { kEncode, kDecode, kDecodedSize, kEncodedSize, kReadMessage };
+enum class Single { kEncode, kDecode, kDecodedSize, kEncodedSize, kReadMessage, kEncodeFramed };
 
 int run_single(Single kind, const uint8_t* in, size_t n, uint8_t* out, size_t slot, uint64_t* len_out,
                uint64_t* used_out, bool reuse_in, uint32_t dialect) {
@@ -322,8 +322,9 @@ int run_single(Single kind, const uint8_t* in, size_t n, uint8_t* out, size_t sl
         if ((st = g_ctx.d_in.reserve(n + 16, kSingleDevice))) return st;
         if ((st = g_ctx.h_in.reserve(n + 16, kSingleStaging))) return st;
     }
-    const bool encodes = kind == Single::kEncode || kind == Single::kEncodedSize;
-    const bool write = kind == Single::kEncode || kind == Single::kDecode || kind == Single::kReadMessage;
+    const bool framed = kind == Single::kEncodeFramed;  // the C++ dialect's: a framed message, piece by piece
+    const bool encodes = kind == Single::kEncode || kind == Single::kEncodedSize || framed;
+    const bool write = kind == Single::kEncode || kind == Single::kDecode || kind == Single::kReadMessage || framed;
     if (write && (st = g_ctx.d_out.reserve(slot + 16, kSingleDevice))) return st;
     // one kernel for a single unit the one-unit kernels take (kFastDecodeMax / kFastEncodeMax)
     const bool one = n > 0 && ((kind == Single::kDecode && n <= kFastDecodeMax) || (encodes && n <= kFastEncodeMax));
@@ -346,6 +347,9 @@ int run_single(Single kind, const uint8_t* in, size_t n, uint8_t* out, size_t sl
     if (one && kind == Single::kDecode)
         e = cpk::launch_decode_one(d_in, m.in_off(), m.in_len(), d_out, m.out_off(), m.out_cap(), m.out_len(),
                                    m.status(), s);
+    else if (framed)
+        e = cpk::launch_encode_framed(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
+                                      m.status(), true, true, nullptr, s);
     else if (encodes && dialect == CAPNP_PACKED_DIALECT_CXX)
         e = cpk::launch_encode_cxx(d_in, m.in_off(), m.in_len(), 1, d_out, m.out_off(), m.out_cap(), m.out_len(),
                                    m.status(), write, s);
@@ -395,6 +399,29 @@ int encode_single(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t*
     st = run_single(Single::kEncode, in, n, out, cap < bound ? cap : bound, &len, nullptr, false, dialect);
     *out_len = (size_t)len;
     return st;
+}
+
+// The per-unit checks of the framed calls on host bytes (the kernels' framed_parse): Message.init's
+// table parse (message.zig:341-394), then the exact-length rule.
+int framed_verdict(const uint8_t* in, size_t n) {
+    if (n % 8) return CAPNP_PACKED_INVALID_MESSAGE_SIZE;
+    if (n < 4) return CAPNP_PACKED_END_OF_STREAM;
+    uint32_t m1;
+    std::memcpy(&m1, in, 4);
+    if (m1 == 0xFFFFFFFFu) return CAPNP_PACKED_INVALID_SEGMENT_COUNT;
+    if (m1 >= 512u) return CAPNP_PACKED_SEGMENT_COUNT_LIMIT_EXCEEDED;
+    const uint64_t count = (uint64_t)m1 + 1, hw = count / 2 + 1;
+    if (8 * hw > n) return CAPNP_PACKED_TRUNCATED_MESSAGE;
+    uint64_t total = hw;
+    for (uint64_t s = 0; s < count; ++s) {
+        uint32_t sw;
+        std::memcpy(&sw, in + 4 + 4 * s, 4);
+        total += sw;
+    }
+    if (total > n / 8) return CAPNP_PACKED_TRUNCATED_MESSAGE;
+    if (total < n / 8) return CAPNP_PACKED_INVALID_ARGUMENT;  // trailing words
+    if (n / 8 > 0xFFFFF000ull) return CAPNP_PACKED_INVALID_ARGUMENT;
+    return CAPNP_PACKED_OK;
 }
 
 int check_batch(const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n, const uint64_t* d_len,
@@ -639,9 +666,83 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
     int st = ensure_device();
     if (st) return st;
     return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
-                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, d_workspace,
-                                             static_cast<hipStream_t>(stream)),
+                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, false,
+                                             d_workspace, static_cast<hipStream_t>(stream)),
                     "dense encode launch");
+}
+
+int capnp_packed_encode_framed(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
+                               uint32_t dialect) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
+    *out_len = 0;
+    if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
+    if (dialect == CAPNP_PACKED_DIALECT_ZIG) {
+        // the framing only adds the checks: on the host's bytes, then packPacked(unit)
+        const int v = framed_verdict(in, n);
+        if (v != CAPNP_PACKED_OK) return fail(v, capnp_packed_status_name(v));
+        return encode_single(in, n, out, cap, out_len, dialect);
+    }
+    if (n % 8) return fail(CAPNP_PACKED_INVALID_MESSAGE_SIZE, "InvalidMessageSize");
+    int st = ensure_device();
+    if (st) return st;
+    std::lock_guard<std::mutex> lock(g_ctx.mu);
+    const size_t bound = capnp_packed_encode_bound(n);
+    uint64_t len = 0;
+    st = run_single(Single::kEncodeFramed, in, n, out, cap < bound ? cap : bound, &len, nullptr, false, dialect);
+    *out_len = (size_t)len;
+    return st;
+}
+
+size_t capnp_packed_encode_framed_workspace_bytes(uint32_t n) { return cpk::framed_workspace_bytes(n); }
+
+// Every argument check answers before any device work.
+int capnp_packed_encode_framed_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                     uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                     const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                     uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (n == 0) return CAPNP_PACKED_OK;
+    if (!d_in_off || !d_in_len || !d_out_len || !d_status)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    const bool write = d_out != nullptr;
+    if (write && (!d_out_off || !d_out_cap)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null output slot arrays");
+    if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the framed encode needs a workspace");
+    int st = check_ws(d_workspace, workspace_bytes, cpk::framed_workspace_bytes(n),
+                      "workspace smaller than capnp_packed_encode_framed_workspace_bytes(n)");
+    if (st) return st;
+    if ((st = ensure_device())) return st;
+    return launched(cpk::launch_encode_framed(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
+                                              d_status, write, dialect == CAPNP_PACKED_DIALECT_CXX, d_workspace,
+                                              static_cast<hipStream_t>(stream)),
+                    "framed encode launch");
+}
+
+// Every argument check answers before any device work.
+int capnp_packed_encode_framed_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                           uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
+                                           uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status,
+                                           uint32_t dialect, void* d_workspace, size_t workspace_bytes,
+                                           void* stream) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (n == 0 && !d_out_off) return CAPNP_PACKED_OK;
+    if (n) {
+        if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
+        int st = check_ws(d_workspace, workspace_bytes, cpk::dense_workspace_bytes(n),
+                          "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
+        if (st) return st;
+    }
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
+                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, true,
+                                             d_workspace, static_cast<hipStream_t>(stream)),
+                    "framed dense encode launch");
 }
 
 size_t capnp_packed_split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound) {

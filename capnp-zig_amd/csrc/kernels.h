@@ -101,7 +101,18 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
 size_t dense_workspace_bytes(uint32_t n);
 hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint8_t* out, uint64_t out_base, uint64_t out_cap, uint64_t* out_off,
-                               uint64_t* out_len, int32_t* status, bool cxx, void* ws, hipStream_t stream);
+                               uint64_t* out_len, int32_t* status, bool cxx, bool framed, void* ws,
+                               hipStream_t stream);
+
+// Framed messages as units (capnp_packed_encode_framed_*): launch_encode_dense's
+// `framed` above, and the slot call here. Each unit is checked as Message.init checks it, plus
+// the exact-length rule; under the C++ dialect its segment table and segments are packed piece
+// by piece. ws: framed_workspace_bytes(n) bytes, 256-B aligned (the Zig dialect's; the C++
+// dialect takes none).
+size_t framed_workspace_bytes(uint32_t n);
+hipError_t launch_encode_framed(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                                uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
+                                int32_t* status, bool write, bool cxx, void* ws, hipStream_t stream);
 
 // Message.init segment-table parse (message.zig:341-394).
 hipError_t launch_message_init(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,

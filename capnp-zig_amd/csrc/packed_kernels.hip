@@ -1230,6 +1230,248 @@ __global__ __launch_bounds__(kBlock) void encode_message_cxx_kernel(const uint64
 }
 
 // ---------------------------------------------------------------------------
+// ENCODE of framed messages (capnp_packed_encode_framed_*): the unit is one
+// framed message (toBytes, message.zig:2123-2170: the segment table, then the segments), and
+// under the C++ dialect its pieces are packed one by one, as encode_message_cxx_kernel packs a
+// segment list. A unit must be exactly its table plus its segments: a stream writer cannot
+// leave trailing words for the reader to take as the next message.
+// ---------------------------------------------------------------------------
+// A loaded u64 of a wave-uniform address, back in scalar registers.
+__device__ __forceinline__ uint64_t framed_uniform64(uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
+}
+
+struct FramedUnit {
+    int32_t st;      // the unit's verdict
+    uint32_t count;  // segments (st OK)
+    uint32_t hw;     // the table's words
+    uint32_t words;  // the unit's words
+};
+
+// Message.init's table parse (message_init_kernel's statuses) plus the exact-length rule, by
+// all lanes of a wave on a wave-uniform unit; every field of the result is wave-uniform. A
+// size is loaded only once 8 * hw <= nbytes is known, so no load leaves the unit.
+__device__ __forceinline__ FramedUnit framed_parse(const uint8_t* src, uint64_t nbytes, uint32_t lane) {
+    FramedUnit f = {ST_OK, 0u, 0u, 0u};
+    if (reinterpret_cast<uintptr_t>(src) & 7) f.st = ST_ARG;
+    else if (nbytes & 7) f.st = ST_SIZE;  // message.zig:201
+    else if (nbytes < 4) f.st = ST_EOS;   // :343 readInt (an empty unit)
+    if (f.st != ST_OK) return f;
+    const uint32_t m1 = __builtin_amdgcn_readfirstlane((uint32_t)gload64(src));
+    if (m1 == 0xFFFFFFFFu) f.st = ST_SEGCOUNT;       // :346
+    else if (m1 >= kMsgMaxSegs) f.st = ST_SEGLIMIT;  // :348
+    if (f.st != ST_OK) return f;
+    f.count = m1 + 1;
+    f.hw = f.count / 2 + 1;
+    if (8ull * f.hw > nbytes) {  // :353
+        f.st = ST_TRUNC;
+        return f;
+    }
+    // lane j sums sizes [8j, 8j + 8) of the at most 512: u32 entry 1 + s of the table
+    uint64_t mine = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 8; ++t) {
+        const uint32_t s = 8 * lane + t;
+        if (s < f.count) mine += *reinterpret_cast<const uint32_t*>(src + 4 + 4 * s);
+    }
+    const uint64_t total = f.hw + wave_sum64(mine);
+    const uint64_t words = nbytes >> 3;
+    if (total > words) f.st = ST_TRUNC;              // :380
+    else if (total < words) f.st = ST_ARG;           // trailing words
+    else if (words > 0xFFFFF000ull) f.st = ST_ARG;   // word indices are u32
+    f.words = (uint32_t)words;
+    return f;
+}
+
+// Where a framed unit is coded. kFrTile: a valid unit of at most one tile that is one piece's
+// worth of bytes (any such unit under the Zig rule; under the C++ rule a single-segment one: its
+// table word (0, size) has four zero bytes, so it is a tag record or, for an empty segment, a
+// zero run of one word with nothing after it, and no run crosses it: DESIGN.md §2.12). kFrWalk:
+// piece by piece, or tile by tile. The slot kernel, the dense kernel and both passes of the
+// dense long kernel all ask this one function.
+enum : uint32_t { kFrFail = 0, kFrTile = 1, kFrWalk = 2 };
+template <bool CXX>
+__device__ __forceinline__ uint32_t framed_route(const FramedUnit& f) {
+    if (f.st != ST_OK) return kFrFail;
+    if (f.words > kEncMaxWords) return kFrWalk;
+    return (CXX && f.count > 1) ? kFrWalk : kFrTile;
+}
+
+// A valid framed unit under the C++ rule, piece by piece: a single-segment unit is one piece
+// (the identity above), else the table and then every segment, each with fresh carries
+// (encode_piece_cxx starts them at zero). Segment s starts at word hw + the sizes before it: at
+// 8 mod 16 when that is odd. The sizes are re-read from the table, wave-uniformly.
+template <bool WRITE>
+__device__ __forceinline__ void framed_walk_cxx(uint8_t* lds, const uint64_t* lut, uint32_t lane, const uint8_t* src,
+                                                const FramedUnit& f, uint8_t* dst, uint64_t cap, uint64_t& pos,
+                                                bool& fits) {
+    if (f.count == 1) {
+        encode_piece_cxx<WRITE>(lds, lut, lane, src, f.words, dst, cap, pos, fits);
+        return;
+    }
+    encode_piece_cxx<WRITE>(lds, lut, lane, src, f.hw, dst, cap, pos, fits);
+    uint64_t at = f.hw;
+    for (uint32_t s = 0; s < f.count; ++s) {  // wave-uniform
+        const uint32_t sw = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(src + 4 + 4 * s));
+        encode_piece_cxx<WRITE>(lds, lut, lane, src + 8 * at, sw, dst, cap, pos, fits);
+        at += sw;
+    }
+}
+
+// The slot call under the C++ dialect, split as encode_cxx_kernel / encode_cxx_long_kernel are
+// (the one-tile kernel keeps its register budget without the piece loop). This kernel, a wave
+// per unit: every unit's verdict, and the kFrTile units (valid single-segment units of at most
+// one tile) through the one-piece code of encode_cxx_kernel. The tile is loaded before the
+// table is parsed, once word 0 allows a single segment (the load stays inside the unit whatever
+// the rest of the table says).
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void encode_framed_cxx_kernel(const uint8_t* __restrict__ in,
+                                                                   const uint64_t* __restrict__ in_off,
+                                                                   const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                   uint8_t* __restrict__ out,
+                                                                   const uint64_t* __restrict__ out_off,
+                                                                   const uint64_t* __restrict__ out_cap,
+                                                                   uint64_t* __restrict__ out_len,
+                                                                   int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint32_t unit = blockIdx.x * kWavesPerBlock + wave;
+    const bool live = unit < n;  // wave-uniform
+    const uint64_t b0 = framed_uniform64(live ? in_off[unit] : 0ull);
+    const uint64_t nbytes = framed_uniform64(live ? in_len[unit] : 0ull);
+    const uint8_t* const src = in + b0;
+    const bool valid = live && !(reinterpret_cast<uintptr_t>(src) & 7) && !(nbytes & 7);
+    // word 0's low half, the count - 1, says whether the unit can be a kFrTile one: only then is
+    // the tile loaded (a multi-segment unit's bytes are the walk kernel's to read, once)
+    const uint32_t fit = valid && (nbytes >> 3) <= kEncMaxWords ? (uint32_t)(nbytes >> 3) : 0u;
+    uint32_t m1 = 1;
+    if (fit) m1 = __builtin_amdgcn_readfirstlane((uint32_t)gload64(src));
+    const uint32_t words = m1 == 0 ? fit : 0u;
+    const bool direct = words == kEncMaxWords && !(reinterpret_cast<uintptr_t>(src) & 15);
+    uint64_t w[8];
+    if (direct) tile_words_direct(w, src, lane);
+    else if (words) encode_stage(lds, src, words, lane);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    }
+    if (!live) return;
+    const FramedUnit f = framed_parse(src, nbytes, lane);
+    const uint32_t route = framed_route<true>(f);
+    if (route == kFrFail) {
+        if (lane == 0) { out_len[unit] = 0; status[unit] = f.st; }
+        return;
+    }
+    if (route == kFrWalk) return;  // encode_framed_cxx_walk_kernel's
+    uint64_t ob = 0, cap = 0;
+    if (WRITE) {
+        ob = out_off[unit];
+        cap = out_cap[unit];
+    }
+    if (!direct) {
+        wave_lds_sync();
+        tile_words_lds(w, lds, lane, words);
+    }
+    uint32_t cz = 0, ch = 0;
+    const uint32_t P = encode_tile_cxx<WRITE>(lds, lut, lane, words, 0, true, cz, ch, words, words, out + ob, cap, w);
+    if (lane == 0) {
+        out_len[unit] = P;
+        status[unit] = (WRITE && (uint64_t)P > cap) ? ST_SPACE : ST_OK;
+    }
+}
+
+// The kFrWalk units of the slot call (multi-segment units, and units of more than one tile),
+// piece by piece, a wave each. They may be most of a batch, so a wave looks at kFramedGroup
+// units per step (a lane each: a superset of kFrWalk by the lengths and word 0's low half, the
+// count - 1) and the grid is sized by that; framed_parse and framed_route then decide.
+constexpr uint32_t kFramedGroup = 4;
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void encode_framed_cxx_walk_kernel(const uint8_t* __restrict__ in,
+                                                                        const uint64_t* __restrict__ in_off,
+                                                                        const uint64_t* __restrict__ in_len,
+                                                                        uint32_t n, uint8_t* __restrict__ out,
+                                                                        const uint64_t* __restrict__ out_off,
+                                                                        const uint64_t* __restrict__ out_cap,
+                                                                        uint64_t* __restrict__ out_len,
+                                                                        int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    }
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kFramedGroup;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kFramedGroup; ubase < n; ubase += stride) {
+        const uint64_t u = ubase + lane;
+        bool mine = false;
+        if (u < n && lane < kFramedGroup) {
+            const uint64_t len = in_len[u];
+            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
+                   (len >> 3) <= 0xFFFFF000ull &&
+                   ((len >> 3) > kEncMaxWords || (uint32_t)gload64(in + in_off[u]) != 0);
+        }
+        uint64_t todo = __ballot(mine);
+        while (todo) {  // wave-uniform
+            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint8_t* const src = in + framed_uniform64(in_off[unit]);
+            const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
+            if (framed_route<true>(f) != kFrWalk) continue;
+            uint64_t ob = 0, cap = 0;
+            if (WRITE) {
+                ob = out_off[unit];
+                cap = out_cap[unit];
+            }
+            uint64_t pos = 0;
+            bool fits = true;
+            framed_walk_cxx<WRITE>(lds, lut, lane, src, f, out + ob, cap, pos, fits);
+            if (lane == 0) {
+                out_len[unit] = pos;
+                status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+            }
+        }
+    }
+}
+
+// The slot call under the Zig dialect: the verdicts and the effective lengths (0 for a failed
+// unit) into the workspace ahead of launch_encode, a wave per unit ...
+__global__ __launch_bounds__(kBlock) void framed_check_kernel(const uint8_t* __restrict__ in,
+                                                              const uint64_t* __restrict__ in_off,
+                                                              const uint64_t* __restrict__ in_len, uint32_t n,
+                                                              uint64_t* __restrict__ eff_len,
+                                                              int32_t* __restrict__ verdict) {
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t unit = blockIdx.x * kWavesPerBlock + wave;
+    if (unit >= n) return;  // wave-uniform
+    const uint64_t len = framed_uniform64(in_len[unit]);
+    const FramedUnit f = framed_parse(in + framed_uniform64(in_off[unit]), len, lane);
+    if (lane == 0) {
+        eff_len[unit] = f.st == ST_OK ? len : 0ull;
+        verdict[unit] = f.st;
+    }
+}
+// ... and the failed units' statuses and zero lengths in place after it.
+__global__ __launch_bounds__(kBlock) void framed_verdict_kernel(const int32_t* __restrict__ verdict, uint32_t n,
+                                                                uint64_t* __restrict__ out_len,
+                                                                int32_t* __restrict__ status) {
+    const uint32_t unit = blockIdx.x * kBlock + threadIdx.x;
+    if (unit >= n) return;
+    const int32_t v = verdict[unit];
+    if (v != ST_OK) {
+        out_len[unit] = 0;
+        status[unit] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // ENCODE into one dense stream (capnp_packed_encode_dense_batch):
 // MessageBuilder.writePackedTo called unit after unit on one writer (message.zig:2209-2213).
 // Unit i's packed bytes start where unit i - 1's end, so a unit's destination is an ordered
@@ -1445,7 +1687,10 @@ __device__ __forceinline__ uint64_t dense_long_zig(uint8_t* lds, const uint64_t*
 }
 
 // One tile of the dense stream: the wave's unit is tile * kDnWaves + wave.
-template <bool WRITE, bool CXX>
+// FRAMED (capnp_packed_encode_framed_dense_batch): the unit is a framed message; framed_parse
+// gives its verdict and framed_route its way (a multi-segment unit under the C++ rule goes with
+// the units of more than one tile).
+template <bool WRITE, bool CXX, bool FRAMED = false>
 __device__ __forceinline__ void dense_tile(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                            const uint64_t* __restrict__ in_len, uint8_t* lds, const uint64_t* lut,
                                            DenseUnit& du) {
@@ -1453,6 +1698,21 @@ __device__ __forceinline__ void dense_tile(const uint8_t* __restrict__ in, const
     const uint32_t unit = du.unit;
     const bool live = du.live;
     const uint64_t b0 = live ? in_off[unit] : 0ull, nbytes = live ? in_len[unit] : 0ull;
+    if constexpr (FRAMED) {
+        const uint8_t* const fsrc = in + framed_uniform64(b0);
+        FramedUnit f = {ST_OK, 0u, 0u, 0u};
+        if (live) f = framed_parse(fsrc, framed_uniform64(nbytes), lane);  // wave-uniform
+        const uint32_t route = framed_route<CXX>(f);
+        du.st = f.st;
+        if (!live || route == kFrFail) {
+            du.resolve(0);
+            return;
+        }
+        if (route == kFrWalk) {  // encode_dense_long_kernel's: sized before, written after
+            du.resolve(du.out_len[unit]);
+            return;
+        }
+    }
     const uint8_t* const src = in + b0;
     int32_t st = ST_OK;
     if (reinterpret_cast<uintptr_t>(src) & 7) st = ST_ARG;
@@ -1554,6 +1814,65 @@ __global__ __launch_bounds__(kBlock) void encode_dense_long_kernel(const uint8_t
     }
 }
 
+// The same two passes over framed messages: the units framed_route sends here (kFrWalk:
+// multi-segment units under the C++ rule too, so they may be most of a batch). A wave looks at
+// kFramedGroup units per step, not 64, and the grid is sized by that (launch_encode_dense), so
+// a batch of walked units does not run 64 to a wave. The lane-wise filter is a superset of
+// kFrWalk (word 0's low half is the count - 1); framed_parse and framed_route then decide, as in
+// encode_framed_dense_kernel. (A kernel of its own, not a template mode of the one above: that
+// one's code stays as it is.)
+template <bool WRITE, bool CXX>
+__global__ __launch_bounds__(kBlock) void encode_framed_dense_long_kernel(const uint8_t* __restrict__ in,
+                                                                          const uint64_t* __restrict__ in_off,
+                                                                          const uint64_t* __restrict__ in_len,
+                                                                          uint32_t n, uint8_t* out,
+                                                                          const uint64_t* out_off, uint64_t* out_len,
+                                                                          const int32_t* status, uint64_t* ws,
+                                                                          uint64_t ws_words) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (WRITE) {
+        lut[threadIdx.x] = compact_selector(threadIdx.x);
+        __syncthreads();
+    } else {
+        // the launch ahead of encode_framed_dense_kernel zeroes its workspace, as above
+        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ws_words; i += (uint64_t)gridDim.x * kBlock)
+            ws[i] = 0;
+    }
+    uint8_t* lds = smem + wave * kEncLds;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kFramedGroup;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kFramedGroup; ubase < n; ubase += stride) {
+        const uint64_t u = ubase + lane;
+        bool mine = false;
+        if (u < n && lane < kFramedGroup) {
+            const uint64_t len = in_len[u];
+            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
+                   (len >> 3) <= 0xFFFFF000ull &&
+                   ((len >> 3) > kEncMaxWords || (CXX && (uint32_t)gload64(in + in_off[u]) != 0));
+            if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
+        }
+        uint64_t todo = __ballot(mine);
+        while (todo) {  // wave-uniform
+            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint8_t* const src = in + framed_uniform64(in_off[unit]);
+            const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
+            if (framed_route<CXX>(f) != kFrWalk) continue;
+            uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
+            uint64_t pos = 0;
+            if (CXX) {
+                bool fits = true;
+                framed_walk_cxx<WRITE>(lds, lut, lane, src, f, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
+            } else {
+                pos = dense_long_zig<WRITE>(lds, lut, lane, src, f.words, dst);
+            }
+            if (!WRITE && lane == 0) out_len[unit] = pos;
+        }
+    }
+}
+
 // Register target: 16 waves are one workgroup per CU (82 KB of LDS), 4 waves per SIMD. (With 8
 // waves the LDS admits three workgroups per CU, 80 VGPRs: the Zig tile fits that, the C++ tile,
 // 95 VGPRs as it comes, does not and runs at two.)
@@ -1599,6 +1918,52 @@ __global__ __launch_bounds__(kDnBlock, (CXX || kDnWaves > 8) ? 4 : 6) void encod
     du.live = unit < n;
     du.unit = du.live ? (uint32_t)unit : 0u;
     dense_tile<WRITE, CXX>(in, in_off, in_len, lds, lut, du);
+}
+
+// The same over framed messages (dense_tile's FRAMED mode), with the same register target. (A
+// kernel of its own: encode_dense_kernel's code stays as it is.)
+template <bool WRITE, bool CXX>
+__global__ __launch_bounds__(kDnBlock, 4) void encode_framed_dense_kernel(const uint8_t* __restrict__ in,
+                                                                const uint64_t* __restrict__ in_off,
+                                                                const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                uint8_t* out, uint64_t out_base, uint64_t out_cap,
+                                                                uint64_t* out_off, uint64_t* out_len,
+                                                                int32_t* status, uint64_t* ws_) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kDnWaves * kEncLds];
+    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
+    __shared__ __attribute__((aligned(16))) uint64_t sx[2 * kDnWaves + 2];
+    dn_gu64* const ws = reinterpret_cast<dn_gu64*>(reinterpret_cast<uintptr_t>(ws_));
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x == 0)
+        sx[2 * kDnWaves + 1] = __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>(ws),
+                                                      1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (WRITE && threadIdx.x < 256) lut[threadIdx.x] = compact_selector(threadIdx.x);
+    __syncthreads();
+    const uint32_t ticket = __builtin_amdgcn_readfirstlane((uint32_t)sx[2 * kDnWaves + 1]);
+    const uint32_t ntiles = (uint32_t)dense_tiles(n);
+    DenseUnit du;
+    du.sx = sx;
+    du.ws = ws;
+    du.out = out;
+    du.out_base = out_base;
+    du.out_cap = out_cap;
+    du.out_off = out_off;
+    du.out_len = out_len;
+    du.status = status;
+    du.ntiles = ntiles;
+    du.n = n;
+    du.wave = wave;
+    du.lane = lane;
+    du.write = WRITE;
+    du.off = 0;
+    uint8_t* const lds = smem + wave * kEncLds;
+    if (ticket >= ntiles) return;  // block-uniform (the grid is ntiles workgroups: never)
+    du.tile = ticket;
+    const uint64_t unit = (uint64_t)ticket * kDnWaves + wave;
+    du.live = unit < n;
+    du.unit = du.live ? (uint32_t)unit : 0u;
+    dense_tile<WRITE, CXX, true>(in, in_off, in_len, lds, lut, du);
 }
 
 __global__ void store_u64_kernel(uint64_t* p, uint64_t v) { *p = v; }
@@ -5716,6 +6081,47 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
     return hipGetLastError();
 }
 
+// Framed messages into slots (capnp_packed_encode_framed_batch). The C++
+// dialect is two kernels: the verdicts and the one-tile single-segment units, then the walked units. The Zig dialect is launch_encode over the effective
+// lengths a check kernel leaves in the workspace (0 for a failed unit, whose slot then stays
+// untouched), and the failed units' verdicts put in place after it. The workspace: the class
+// workspace launch_encode takes, then n u64 lengths, then n i32 verdicts, each part 256-B aligned.
+static size_t framed_round256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t framed_workspace_bytes(uint32_t n) {
+    return framed_round256(queue_bytes(n)) + framed_round256(8 * (size_t)n) + framed_round256(4 * (size_t)n);
+}
+
+hipError_t launch_encode_framed(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                                uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
+                                int32_t* status, bool write, bool cxx, void* ws, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (cxx) {
+        // the walked units: a grid of kFramedGroup units a wave and step, up to a few times the resident one
+        const uint64_t per_block = (uint64_t)kWavesPerBlock * kFramedGroup;
+        const uint32_t walk_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + per_block - 1) / per_block, 4096);
+        with_bool(write, [&](auto w) {
+            constexpr bool W = decltype(w)::value;
+            encode_framed_cxx_kernel<W><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                       out_len, status);
+            encode_framed_cxx_walk_kernel<W><<<walk_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off,
+                                                                                 out_cap, out_len, status);
+        });
+        return hipGetLastError();
+    }
+    uint8_t* const w8 = static_cast<uint8_t*>(ws);
+    const size_t qb = framed_round256(queue_bytes(n));
+    uint64_t* const eff_len = reinterpret_cast<uint64_t*>(w8 + qb);
+    int32_t* const verdict = reinterpret_cast<int32_t*>(w8 + qb + framed_round256(8 * (size_t)n));
+    framed_check_kernel<<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, eff_len, verdict);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_encode(in, in_off, eff_len, n, out, out_off, out_cap, out_len, status, write, ws, queue_bytes(n), stream);
+    if (e != hipSuccess) return e;
+    framed_verdict_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(verdict, n, out_len, status);
+    return hipGetLastError();
+}
+
 // The dense stream (encode_dense_kernel): the ticket, the give-up word and every descriptor are
 // zeroed on every call, ahead of the launch, by the long units' size pass (the whole workspace,
 // a multiple of 256 bytes). Not by hipMemsetAsync: captured by torch.cuda.graph, its node
@@ -5727,7 +6133,8 @@ size_t dense_workspace_bytes(uint32_t n) {
 
 hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint8_t* out, uint64_t out_base, uint64_t out_cap, uint64_t* out_off,
-                               uint64_t* out_len, int32_t* status, bool cxx, void* ws, hipStream_t stream) {
+                               uint64_t* out_len, int32_t* status, bool cxx, bool framed, void* ws,
+                               hipStream_t stream) {
     if (n == 0) {
         if (!out_off) return hipSuccess;
         store_u64_kernel<<<1, 1, 0, stream>>>(out_off, out_base);
@@ -5738,6 +6145,26 @@ hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const 
     // the units of more than one tile: their sizes before, their bytes after (no such unit: one
     // pass over the lengths each)
     const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
+    if (framed) {
+        // framed messages: the walked units may be most of the batch, so the long grid gives every
+        // wave kFramedGroup units a step (up to a grid a few times the resident one)
+        const uint64_t per_block = (uint64_t)kWavesPerBlock * kFramedGroup;
+        const uint32_t walk_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + per_block - 1) / per_block, 4096);
+        with_bool(cxx, [&](auto c) {
+            constexpr bool C = decltype(c)::value;
+            const auto dense_long = [&](auto w) {
+                encode_framed_dense_long_kernel<decltype(w)::value, C><<<walk_blocks, kBlock, 0, stream>>>(
+                    in, in_off, in_len, n, out, out_off, out_len, status, w64, dense_workspace_bytes(n) / 8);
+            };
+            dense_long(std::false_type{});
+            with_bool(out != nullptr, [&](auto w) {
+                encode_framed_dense_kernel<decltype(w)::value, C><<<blocks, kDnBlock, 0, stream>>>(
+                    in, in_off, in_len, n, out, out_base, out_cap, out_off, out_len, status, w64);
+            });
+            if (out) dense_long(std::true_type{});
+        });
+        return hipGetLastError();
+    }
     with_bool(cxx, [&](auto c) {
         constexpr bool C = decltype(c)::value;
         const auto dense_long = [&](auto w) {

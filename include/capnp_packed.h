@@ -50,7 +50,10 @@ extern "C" {
  *   2, additions only: capnp_packed_encode_dense_workspace_bytes and
  *     capnp_packed_encode_dense_batch (the batch form of writePackedTo).
  *   2, additions only: capnp_packed_split_workspace_bytes and capnp_packed_split_streams (dense
- *     streams of packed messages split into their messages: the reader's half of the above). */
+ *     streams of packed messages split into their messages: the reader's half of the above).
+ *   2, additions only: capnp_packed_encode_framed, capnp_packed_encode_framed_workspace_bytes,
+ *     capnp_packed_encode_framed_batch and capnp_packed_encode_framed_dense_batch (the encoders
+ *     over framed messages: under DIALECT_CXX the bytes of capnp convert binary:packed). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -423,6 +426,60 @@ int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_of
                                     uint64_t* d_out_off /* n + 1 */, uint64_t* d_out_len /* n */,
                                     int32_t* d_status /* n */, uint32_t dialect, void* d_workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Framed messages as units: capnp_packed_encode_dialect,
+ * capnp_packed_encode_batch_dialect and capnp_packed_encode_dense_batch with the framing known.
+ * A unit is ONE framed message, the bytes toBytes writes (message.zig:2123-2170) and
+ * Message.init parses (:341-394): the segment table (u32 count - 1, u32 words of each segment,
+ * padded to a word), then the segments back to back. The framing is an argument of its own,
+ * orthogonal to the dialect:
+ *   DIALECT_CXX  the table (8 * ceil((1 + count) / 2) bytes) is packed as one piece, then every
+ *                segment as a piece of its own: byte for byte what capnp convert binary:packed
+ *                and pycapnp write for the message, and what
+ *                capnp_packed_encode_message_batch_dialect writes from its segment list. (The
+ *                unframed calls pack the whole unit as one piece, which differs for about half
+ *                of all multi-segment messages and never for a single-segment one.)
+ *   DIALECT_ZIG  packPacked(unit), exactly the unframed calls' bytes; the framing adds the checks.
+ * Any other dialect: INVALID_ARGUMENT before any device work.
+ * Per-unit checks, in this order; a failed unit gets d_out_len 0 and writes nothing (its slot
+ * stays untouched; in the dense call it takes no bytes and the stream goes on):
+ *   word side not 8-aligned          INVALID_ARGUMENT
+ *   len % 8 != 0                     INVALID_MESSAGE_SIZE
+ *   the table parse, as capnp_packed_message_init_batch: END_OF_STREAM (fewer than 4 bytes: an
+ *     empty unit), INVALID_SEGMENT_COUNT, SEGMENT_COUNT_LIMIT_EXCEEDED (more than 512),
+ *     TRUNCATED_MESSAGE (the table or a segment runs past the unit)
+ *   words after the last segment     INVALID_ARGUMENT (Message.init ignores them; a stream
+ *                                    writer must not: readPackedMessage would take them as the
+ *                                    next message)
+ *   more than 0xFFFFF000 words       INVALID_ARGUMENT
+ * The table's padding half-word is packed as it stands, not checked. No load leaves the unit
+ * beyond the aligned 16-byte lines it touches.
+ * Every OK unit's output is exactly one packed message: capnp_packed_read_message_batch consumes
+ * it whole (consumed == d_out_len, framed length == d_in_len).
+ * Everything else is the mirrored call's contract: OUT_OF_SPACE reports the required size and
+ * nothing is written at or past the capacity; d_out == NULL gives sizes only; the dense call
+ * keeps the out_cap cut and the accumulating offsets (d_out_off has n + 1 entries). The batch
+ * calls are asynchronous on `stream`, allocate nothing and keep no library state, so they are
+ * capturable in a hipGraph. d_workspace is caller-owned device memory, 256-B aligned, required
+ * for n > 0 (NULL, misaligned or short: INVALID_ARGUMENT): the slot call needs
+ * capnp_packed_encode_framed_workspace_bytes(n) bytes, the dense call
+ * capnp_packed_encode_dense_workspace_bytes(n). Two calls in flight must not share one.
+ * n == 0 is OK with NULL arrays. capnp_packed_encode_framed is the host call for one message
+ * (arguments as capnp_packed_encode_dialect).
+ * ------------------------------------------------------------------------ */
+int capnp_packed_encode_framed(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
+                               uint32_t dialect);
+size_t capnp_packed_encode_framed_workspace_bytes(uint32_t n);
+int capnp_packed_encode_framed_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                     uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                     const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                     uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream);
+int capnp_packed_encode_framed_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                           uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
+                                           uint64_t* d_out_off /* n + 1 */, uint64_t* d_out_len /* n */,
+                                           int32_t* d_status /* n */, uint32_t dialect, void* d_workspace,
+                                           size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Dense streams of packed messages split into their messages: what repeated

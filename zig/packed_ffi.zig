@@ -54,6 +54,7 @@ extern "capnp_packed" fn capnp_packed_encode(in: [*]const u8, n: usize, out: [*]
 pub const dialect_zig: u32 = 0;
 pub const dialect_cxx: u32 = 1;
 extern "capnp_packed" fn capnp_packed_encode_dialect(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize, dialect: u32) c_int;
+extern "capnp_packed" fn capnp_packed_encode_framed(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize, dialect: u32) c_int;
 extern "capnp_packed" fn capnp_packed_decoded_size(in: [*]const u8, n: usize, out_size: *usize) c_int;
 extern "capnp_packed" fn capnp_packed_decode(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize) c_int;
 extern "capnp_packed" fn capnp_packed_read_message(in: [*]const u8, n: usize, out: [*]u8, cap: usize, out_len: *usize, consumed: *usize) c_int;
@@ -161,6 +162,25 @@ pub extern "capnp_packed" fn capnp_packed_encode_batch_dialect(
 /// bytes of device memory, 256-B aligned, not shared between calls in flight.
 pub extern "capnp_packed" fn capnp_packed_encode_dense_workspace_bytes(n: u32) usize;
 pub extern "capnp_packed" fn capnp_packed_encode_dense_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    d_out: ?[*]u8, out_base: u64, out_cap: u64,
+    d_out_off: [*]u64, d_out_len: [*]u64, d_status: [*]i32,
+    dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
+) c_int;
+/// The encoders over framed messages (one unit = one toBytes output): the unit is checked as
+/// Message.init checks it, must be exactly its table plus its segments, and under dialect_cxx its
+/// segment table and every segment are packed as pieces of their own (the bytes of
+/// `capnp convert binary:packed`). Arguments as the unframed calls'; the slot call's workspace is
+/// capnp_packed_encode_framed_workspace_bytes(n), the dense call's
+/// capnp_packed_encode_dense_workspace_bytes(n).
+pub extern "capnp_packed" fn capnp_packed_encode_framed_workspace_bytes(n: u32) usize;
+pub extern "capnp_packed" fn capnp_packed_encode_framed_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64,
+    d_out_len: [*]u64, d_status: [*]i32,
+    dialect: u32, d_ws: ?*anyopaque, ws_bytes: usize, stream: ?*anyopaque,
+) c_int;
+pub extern "capnp_packed" fn capnp_packed_encode_framed_dense_batch(
     d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
     d_out: ?[*]u8, out_base: u64, out_cap: u64,
     d_out_off: [*]u64, d_out_len: [*]u64, d_status: [*]i32,
@@ -308,12 +328,29 @@ pub fn packPacked(allocator: std.mem.Allocator, bytes: []const u8) Error![]u8 {
 
 /// packPacked with the C++ capnp packer's bytes (`bytes` as one piece): for files kept beside
 /// ones `capnp convert binary:packed` or pycapnp wrote. Every unpackPacked reads them.
+/// One piece: a framed message of more than one segment packed this way is a valid packed stream
+/// but not the C++ writer's bytes, which restart at the segment table and at every segment;
+/// packMessage below writes those.
 pub fn packPackedCxx(allocator: std.mem.Allocator, bytes: []const u8) Error![]u8 {
     if (bytes.len % 8 != 0) return error.InvalidMessageSize;
     const buf = try allocator.alloc(u8, capnp_packed_encode_bound(bytes.len));
     errdefer allocator.free(buf);
     var len: usize = 0;
     try check(capnp_packed_encode_dialect(bytes.ptr, bytes.len, buf.ptr, buf.len, &len, dialect_cxx));
+    return allocator.realloc(buf, len);
+}
+
+/// One framed message (toBytes' bytes) packed: with `dialect_cxx` byte for byte what the C++
+/// message writer and pycapnp write (the segment table and each segment as pieces of their own),
+/// with `dialect_zig` packPacked(framed). The message must be exactly its table plus its segments:
+/// the reference error set plus the table's errors (EndOfStream, InvalidSegmentCount,
+/// SegmentCountLimitExceeded, TruncatedMessage) and InvalidArgument for trailing words.
+pub fn packMessage(allocator: std.mem.Allocator, framed: []const u8, dialect: u32) Error![]u8 {
+    if (framed.len % 8 != 0) return error.InvalidMessageSize;
+    const buf = try allocator.alloc(u8, capnp_packed_encode_bound(framed.len));
+    errdefer allocator.free(buf);
+    var len: usize = 0;
+    try check(capnp_packed_encode_framed(framed.ptr, framed.len, buf.ptr, buf.len, &len, dialect));
     return allocator.realloc(buf, len);
 }
 
