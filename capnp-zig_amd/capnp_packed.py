@@ -969,12 +969,15 @@ def _units(in_off, *per_unit) -> int:
     return n
 
 
+def _ws_tensor(nbytes: int, device):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
 def workspace(n_units: int, device="cuda"):
     """Device workspace for the *_batch_ws calls (capnp_packed_batch_workspace_bytes):
     a batch that uses its own workspace shares no library state, so a captured
     hipGraph of it may replay beside any other work."""
-    nbytes = lib().capnp_packed_batch_workspace_bytes(n_units)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _ws_tensor(lib().capnp_packed_batch_workspace_bytes(n_units), device)
 
 
 def _ws(ws):
@@ -1008,8 +1011,7 @@ def encode_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status,
 def dense_workspace(n_units: int, device="cuda"):
     """Device workspace of encode_dense_batch (capnp_packed_encode_dense_workspace_bytes); the
     call zeroes it itself. Two calls in flight must not share one."""
-    nbytes = lib().capnp_packed_encode_dense_workspace_bytes(n_units)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _ws_tensor(lib().capnp_packed_encode_dense_workspace_bytes(n_units), device)
 
 
 def encode_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, base=0, cap=None, stream=None,
@@ -1020,6 +1022,12 @@ def encode_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, ba
     are per unit. cap: the stream may use d_out[0 : cap) (None: all of d_out); a unit that
     would end past it is not written and gets OUT_OF_SPACE, the offsets go on. d_out=None:
     sizes and offsets only. ws: a dense_workspace() tensor (None: one is allocated for the call)."""
+    _encode_dense("encode_dense_batch", d_in, in_off, in_len, d_out, out_off, out_len, status, base, cap, stream, ws,
+                  dialect)
+
+
+def _encode_dense(name, d_in, in_off, in_len, d_out, out_off, out_len, status, base, cap, stream, ws, dialect):
+    """encode_dense_batch / encode_framed_dense_batch through the library's capnp_packed_<name>."""
     d = _dialect(dialect)
     n = _units(in_off, in_len, out_len, status)
     if out_off is not None and out_off.numel() < n + 1:
@@ -1028,16 +1036,15 @@ def encode_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, status, ba
         cap = 0 if d_out is None else d_out.numel()
     if ws is None and n:
         ws = dense_workspace(n, device=in_off.device)
-    _raise(lib().capnp_packed_encode_dense_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base, cap,
-                                                 _ptr(out_off), _ptr(out_len), _ptr(status), d, *_ws(ws),
-                                                 _stream(stream)), "encode_dense_batch")
+    fn = getattr(lib(), "capnp_packed_" + name)
+    _raise(fn(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base, cap, _ptr(out_off), _ptr(out_len),
+              _ptr(status), d, *_ws(ws), _stream(stream)), name)
 
 
 def framed_workspace(n_units: int, device="cuda"):
     """Device workspace of encode_framed_batch (capnp_packed_encode_framed_workspace_bytes). Two
     calls in flight must not share one."""
-    nbytes = lib().capnp_packed_encode_framed_workspace_bytes(n_units)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _ws_tensor(lib().capnp_packed_encode_framed_workspace_bytes(n_units), device)
 
 
 def encode_framed_batch(d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status, stream=None, ws=None,
@@ -1064,17 +1071,8 @@ def encode_framed_dense_batch(d_in, in_off, in_len, d_out, out_off, out_len, sta
     form of writing message after message to one packed stream; with dialect="cxx" the stream is
     byte for byte what capnp convert binary:packed writes. A failed unit takes no bytes. ws: a
     dense_workspace() tensor (None: one is allocated for the call)."""
-    d = _dialect(dialect)
-    n = _units(in_off, in_len, out_len, status)
-    if out_off is not None and out_off.numel() < n + 1:
-        raise InvalidArgument(f"out_off has {out_off.numel()} entries for {n} units (n + 1 needed)")
-    if cap is None:
-        cap = 0 if d_out is None else d_out.numel()
-    if ws is None and n:
-        ws = dense_workspace(n, device=in_off.device)
-    _raise(lib().capnp_packed_encode_framed_dense_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(d_out), base,
-                                                        cap, _ptr(out_off), _ptr(out_len), _ptr(status), d, *_ws(ws),
-                                                        _stream(stream)), "encode_framed_dense_batch")
+    _encode_dense("encode_framed_dense_batch", d_in, in_off, in_len, d_out, out_off, out_len, status, base, cap,
+                  stream, ws, dialect)
 
 
 def write_packed_messages(frames, dialect="zig", device="cuda") -> bytes:
@@ -1159,8 +1157,7 @@ def split_workspace(n: int, in_bytes_bound: int, device="cuda"):
     at most in_bytes_bound packed bytes in all; the call sets it up itself. The bound sizes the
     window tables only: a smaller one (0 included) costs time on long streams, never results.
     Two calls in flight must not share one."""
-    nbytes = lib().capnp_packed_split_workspace_bytes(n, in_bytes_bound)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _ws_tensor(lib().capnp_packed_split_workspace_bytes(n, in_bytes_bound), device)
 
 
 def split_streams(d_in, in_off, in_len, msg_first, msg_off, msg_len, msg_framed, consumed, status,

@@ -424,6 +424,12 @@ int framed_verdict(const uint8_t* in, size_t n) {
     return CAPNP_PACKED_OK;
 }
 
+int check_dialect(uint32_t dialect) {
+    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    return CAPNP_PACKED_OK;
+}
+
 int check_batch(const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n, const uint64_t* d_len,
                 const int32_t* d_status) {
     if (n == 0) return CAPNP_PACKED_OK;
@@ -476,6 +482,30 @@ int encode_message_batch(const uint64_t* d_seg_ptr, const uint64_t* d_seg_len, c
                     "encode-message launch");
 }
 
+// capnp_packed_encode_dense_batch and capnp_packed_encode_framed_dense_batch. Every argument
+// check answers before any device work.
+int encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
+                       uint8_t* d_out, uint64_t out_base, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len,
+                       int32_t* d_status, uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream,
+                       bool framed, const char* what) {
+    if (int st = check_dialect(dialect)) return st;
+    if (n == 0 && !d_out_off) return CAPNP_PACKED_OK;
+    if (n) {
+        if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
+        int st = check_ws(d_workspace, workspace_bytes, cpk::dense_workspace_bytes(n),
+                          "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
+        if (st) return st;
+    }
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
+                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, framed,
+                                             d_workspace, static_cast<hipStream_t>(stream)),
+                    what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -521,8 +551,7 @@ int capnp_packed_encode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, s
 
 int capnp_packed_encode_dialect(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
                                 uint32_t dialect) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (int st = check_dialect(dialect)) return st;
     return encode_single(in, n, out, cap, out_len, dialect);
 }
 
@@ -625,8 +654,7 @@ int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_
                                       uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
                                       const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
                                       uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (int st = check_dialect(dialect)) return st;
     if (dialect == CAPNP_PACKED_DIALECT_ZIG) {
         if (d_out)
             return capnp_packed_encode_batch_ws(d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len,
@@ -647,34 +675,17 @@ int capnp_packed_encode_batch_dialect(const uint8_t* d_in, const uint64_t* d_in_
 
 size_t capnp_packed_encode_dense_workspace_bytes(uint32_t n) { return cpk::dense_workspace_bytes(n); }
 
-// Every argument check answers before any device work.
 int capnp_packed_encode_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                     uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
                                     uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
                                     void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
-    if (n == 0 && !d_out_off) return CAPNP_PACKED_OK;
-    if (n) {
-        if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
-            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
-        int st = check_ws(d_workspace, workspace_bytes, cpk::dense_workspace_bytes(n),
-                          "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
-        if (st) return st;
-    }
-    int st = ensure_device();
-    if (st) return st;
-    return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
-                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, false,
-                                             d_workspace, static_cast<hipStream_t>(stream)),
-                    "dense encode launch");
+    return encode_dense_batch(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off, d_out_len, d_status,
+                              dialect, d_workspace, workspace_bytes, stream, false, "dense encode launch");
 }
 
 int capnp_packed_encode_framed(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
                                uint32_t dialect) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (int st = check_dialect(dialect)) return st;
     if (!out_len) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "out_len is null");
     *out_len = 0;
     if ((n && !in) || (cap && !out)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null buffer");
@@ -702,8 +713,7 @@ int capnp_packed_encode_framed_batch(const uint8_t* d_in, const uint64_t* d_in_o
                                      uint32_t n, uint8_t* d_out, const uint64_t* d_out_off,
                                      const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
                                      uint32_t dialect, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (int st = check_dialect(dialect)) return st;
     if (n == 0) return CAPNP_PACKED_OK;
     if (!d_in_off || !d_in_len || !d_out_len || !d_status)
         return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
@@ -720,29 +730,13 @@ int capnp_packed_encode_framed_batch(const uint8_t* d_in, const uint64_t* d_in_o
                     "framed encode launch");
 }
 
-// Every argument check answers before any device work.
 int capnp_packed_encode_framed_dense_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                            uint32_t n, uint8_t* d_out, uint64_t out_base, uint64_t out_cap,
                                            uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status,
                                            uint32_t dialect, void* d_workspace, size_t workspace_bytes,
                                            void* stream) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
-    if (n == 0 && !d_out_off) return CAPNP_PACKED_OK;
-    if (n) {
-        if (!d_in_off || !d_in_len || !d_out_off || !d_out_len || !d_status)
-            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-        if (!d_workspace) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "the dense encode needs a workspace");
-        int st = check_ws(d_workspace, workspace_bytes, cpk::dense_workspace_bytes(n),
-                          "workspace smaller than capnp_packed_encode_dense_workspace_bytes(n)");
-        if (st) return st;
-    }
-    int st = ensure_device();
-    if (st) return st;
-    return launched(cpk::launch_encode_dense(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off,
-                                             d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, true,
-                                             d_workspace, static_cast<hipStream_t>(stream)),
-                    "framed dense encode launch");
+    return encode_dense_batch(d_in, d_in_off, d_in_len, n, d_out, out_base, out_cap, d_out_off, d_out_len, d_status,
+                              dialect, d_workspace, workspace_bytes, stream, true, "framed dense encode launch");
 }
 
 size_t capnp_packed_split_workspace_bytes(uint32_t n, uint64_t in_bytes_bound) {
@@ -846,8 +840,7 @@ int capnp_packed_encode_message_batch_dialect(const uint64_t* d_seg_ptr, const u
                                               uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                               uint64_t* d_out_len, int32_t* d_status, uint32_t dialect,
                                               void* stream) {
-    if (dialect != CAPNP_PACKED_DIALECT_ZIG && dialect != CAPNP_PACKED_DIALECT_CXX)
-        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown dialect");
+    if (int st = check_dialect(dialect)) return st;
     return encode_message_batch(d_seg_ptr, d_seg_len, d_seg_first, d_seg_count, n, d_out, d_out_off, d_out_cap,
                                 d_out_len, d_status, dialect == CAPNP_PACKED_DIALECT_CXX, stream);
 }

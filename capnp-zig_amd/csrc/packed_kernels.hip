@@ -55,7 +55,10 @@
 // what it leans on and are no-ops by then. The sections still in this file and the includes
 // between them, in this order, are the object's function order, so neither a section nor an
 // include may move: the banner-marked sections of the encoders, the decoders, the class pass,
-// validate, the framer and the splitter, then the launchers.
+// validate, the framer and the splitter, then the launchers. (The framed encoders are the FRAMED
+// mode of encode_cxx_kernel, encode_cxx_long_kernel, encode_dense_kernel and encode_dense_long_kernel:
+// four names less than the order had, and the first two now stand below the framed helpers, after
+// encode_message_cxx_kernel. Every kernel's code is what it was: DESIGN.md §2.12.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1047,116 +1050,6 @@ __device__ __forceinline__ bool encode_cxx_long_unit(const uint8_t* in, uint64_t
     return !(reinterpret_cast<uintptr_t>(in + off) & 7) && !(len & 7) && (len >> 3) > kEncMaxWords;
 }
 
-// A wave per unit of the batch: every unit of at most one tile (units of at most 64 words too:
-// DESIGN.md §2.9) and the statuses of invalid ones.
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void encode_cxx_kernel(const uint8_t* __restrict__ in,
-                                                            const uint64_t* __restrict__ in_off,
-                                                            const uint64_t* __restrict__ in_len, uint32_t n,
-                                                            uint8_t* __restrict__ out,
-                                                            const uint64_t* __restrict__ out_off,
-                                                            const uint64_t* __restrict__ out_cap,
-                                                            uint64_t* __restrict__ out_len,
-                                                            int32_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
-    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
-    const uint32_t lane = lane_id();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint8_t* lds = smem + wave * kEncLds;
-    const uint32_t unit = blockIdx.x * kWavesPerBlock + wave;
-    const bool live = unit < n;  // wave-uniform
-    const uint64_t b0 = live ? in_off[unit] : 0ull, nbytes = live ? in_len[unit] : 0ull;
-    const uint8_t* const src = in + b0;
-    const bool valid = live && !(reinterpret_cast<uintptr_t>(src) & 7) && !(nbytes & 7);
-    const uint32_t words = valid && (nbytes >> 3) <= kEncMaxWords ? (uint32_t)(nbytes >> 3) : 0u;
-    // a full 16-B aligned tile (every unit of the headline): the lane's 64 B straight from memory,
-    // in flight while the block builds its selector table; else staged through LDS
-    const bool direct = words == kEncMaxWords && !(reinterpret_cast<uintptr_t>(src) & 15);
-    uint64_t w[8];
-    if (direct) tile_words_direct(w, src, lane);
-    else if (words) encode_stage(lds, src, words, lane);
-    if (WRITE) {
-        lut[threadIdx.x] = compact_selector(threadIdx.x);
-        __syncthreads();
-    }
-    if (!live) return;
-    if (!valid) {
-        if (lane == 0) { out_len[unit] = 0; status[unit] = (reinterpret_cast<uintptr_t>(src) & 7) ? ST_ARG : ST_SIZE; }
-        return;
-    }
-    if ((nbytes >> 3) > kEncMaxWords) return;  // encode_cxx_long_kernel's
-    uint64_t ob = 0, cap = 0;
-    if (WRITE) {
-        ob = out_off[unit];
-        cap = out_cap[unit];
-    }
-    if (!direct) {
-        wave_lds_sync();
-        tile_words_lds(w, lds, lane, words);
-    }
-    uint32_t cz = 0, ch = 0;
-    const uint32_t P = encode_tile_cxx<WRITE>(lds, lut, lane, words, 0, true, cz, ch, words, words, out + ob, cap, w);
-    if (lane == 0) {
-        out_len[unit] = P;
-        status[unit] = (WRITE && (uint64_t)P > cap) ? ST_SPACE : ST_OK;
-    }
-}
-
-// The units of more than one tile (encode_cxx_long_unit), found by a small grid that strides
-// over the batch's lengths, 64 per load, and coded a wave each, tile by tile.
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void encode_cxx_long_kernel(const uint8_t* __restrict__ in,
-                                                                 const uint64_t* __restrict__ in_off,
-                                                                 const uint64_t* __restrict__ in_len, uint32_t n,
-                                                                 uint8_t* __restrict__ out,
-                                                                 const uint64_t* __restrict__ out_off,
-                                                                 const uint64_t* __restrict__ out_cap,
-                                                                 uint64_t* __restrict__ out_len,
-                                                                 int32_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
-    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
-    const uint32_t lane = lane_id();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (WRITE) {
-        lut[threadIdx.x] = compact_selector(threadIdx.x);
-        __syncthreads();
-    }
-    uint8_t* lds = smem + wave * kEncLds;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kWave;
-    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kWave; ubase < n; ubase += stride) {
-        const uint64_t u = ubase + lane;
-        uint64_t todo = __ballot(u < n && encode_cxx_long_unit(in, in_off[u < n ? u : 0], in_len[u < n ? u : 0]));
-        while (todo) {  // wave-uniform
-            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
-            todo &= todo - 1;
-            const uint8_t* const src = in + in_off[unit];
-            const uint64_t nwords = in_len[unit] >> 3;
-            uint64_t ob = 0, cap = 0;
-            if (WRITE) {
-                ob = out_off[unit];
-                cap = out_cap[unit];
-            }
-            uint64_t pos = 0;
-            bool fits = true;
-            if (nwords > 0xFFFFF000ull) {  // word indices are u32: one lane
-                if (lane == 0) {
-                    pos = serial_pack_cxx(src, nwords, nullptr);
-                    if (WRITE) {
-                        fits = pos <= cap;
-                        if (fits) serial_pack_cxx(src, nwords, out + ob);
-                    }
-                }
-            } else {
-                encode_piece_cxx<WRITE>(lds, lut, lane, src, (uint32_t)nwords, out + ob, cap, pos, fits);
-            }
-            if (lane == 0) {
-                out_len[unit] = pos;
-                status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
-            }
-        }
-    }
-}
-
 // MessageBuilder.toPackedBytes under the C++ dialect, a wave per message: the segment table
 // (built in the tile's LDS rows) is the first piece, then every segment in order.
 template <bool WRITE>
@@ -1319,21 +1212,21 @@ __device__ __forceinline__ void framed_walk_cxx(uint8_t* lds, const uint64_t* lu
     }
 }
 
-// The slot call under the C++ dialect, split as encode_cxx_kernel / encode_cxx_long_kernel are
-// (the one-tile kernel keeps its register budget without the piece loop). This kernel, a wave
-// per unit: every unit's verdict, and the kFrTile units (valid single-segment units of at most
-// one tile) through the one-piece code of encode_cxx_kernel. The tile is loaded before the
-// table is parsed, once word 0 allows a single segment (the load stays inside the unit whatever
-// the rest of the table says).
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void encode_framed_cxx_kernel(const uint8_t* __restrict__ in,
-                                                                   const uint64_t* __restrict__ in_off,
-                                                                   const uint64_t* __restrict__ in_len, uint32_t n,
-                                                                   uint8_t* __restrict__ out,
-                                                                   const uint64_t* __restrict__ out_off,
-                                                                   const uint64_t* __restrict__ out_cap,
-                                                                   uint64_t* __restrict__ out_len,
-                                                                   int32_t* __restrict__ status) {
+// A wave per unit of the batch: every unit of at most one tile (units of at most 64 words too:
+// DESIGN.md §2.9) and the statuses of invalid ones.
+// FRAMED (capnp_packed_encode_framed_batch): every unit's verdict (framed_parse), and the
+// kFrTile units (valid single-segment units of at most one tile) through the same one-piece
+// code. The tile is loaded before the table is parsed, once word 0 allows a single segment (the
+// load stays inside the unit whatever the rest of the table says).
+template <bool WRITE, bool FRAMED>
+__global__ __launch_bounds__(kBlock) void encode_cxx_kernel(const uint8_t* __restrict__ in,
+                                                            const uint64_t* __restrict__ in_off,
+                                                            const uint64_t* __restrict__ in_len, uint32_t n,
+                                                            uint8_t* __restrict__ out,
+                                                            const uint64_t* __restrict__ out_off,
+                                                            const uint64_t* __restrict__ out_cap,
+                                                            uint64_t* __restrict__ out_len,
+                                                            int32_t* __restrict__ status) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
     __shared__ __attribute__((aligned(16))) uint64_t lut[256];
     const uint32_t lane = lane_id();
@@ -1341,16 +1234,23 @@ __global__ __launch_bounds__(kBlock) void encode_framed_cxx_kernel(const uint8_t
     uint8_t* lds = smem + wave * kEncLds;
     const uint32_t unit = blockIdx.x * kWavesPerBlock + wave;
     const bool live = unit < n;  // wave-uniform
-    const uint64_t b0 = framed_uniform64(live ? in_off[unit] : 0ull);
-    const uint64_t nbytes = framed_uniform64(live ? in_len[unit] : 0ull);
+    uint64_t b0 = live ? in_off[unit] : 0ull, nbytes = live ? in_len[unit] : 0ull;
+    if constexpr (FRAMED) {
+        b0 = framed_uniform64(b0);
+        nbytes = framed_uniform64(nbytes);
+    }
     const uint8_t* const src = in + b0;
     const bool valid = live && !(reinterpret_cast<uintptr_t>(src) & 7) && !(nbytes & 7);
-    // word 0's low half, the count - 1, says whether the unit can be a kFrTile one: only then is
-    // the tile loaded (a multi-segment unit's bytes are the walk kernel's to read, once)
-    const uint32_t fit = valid && (nbytes >> 3) <= kEncMaxWords ? (uint32_t)(nbytes >> 3) : 0u;
-    uint32_t m1 = 1;
-    if (fit) m1 = __builtin_amdgcn_readfirstlane((uint32_t)gload64(src));
-    const uint32_t words = m1 == 0 ? fit : 0u;
+    uint32_t words = valid && (nbytes >> 3) <= kEncMaxWords ? (uint32_t)(nbytes >> 3) : 0u;
+    if constexpr (FRAMED) {
+        // word 0's low half, the count - 1, says whether the unit can be a kFrTile one: only then
+        // is the tile loaded (a multi-segment unit's bytes are the long kernel's to read, once)
+        uint32_t m1 = 1;
+        if (words) m1 = __builtin_amdgcn_readfirstlane((uint32_t)gload64(src));
+        if (m1 != 0) words = 0u;
+    }
+    // a full 16-B aligned tile (every unit of the headline): the lane's 64 B straight from memory,
+    // in flight while the block builds its selector table; else staged through LDS
     const bool direct = words == kEncMaxWords && !(reinterpret_cast<uintptr_t>(src) & 15);
     uint64_t w[8];
     if (direct) tile_words_direct(w, src, lane);
@@ -1360,13 +1260,21 @@ __global__ __launch_bounds__(kBlock) void encode_framed_cxx_kernel(const uint8_t
         __syncthreads();
     }
     if (!live) return;
-    const FramedUnit f = framed_parse(src, nbytes, lane);
-    const uint32_t route = framed_route<true>(f);
-    if (route == kFrFail) {
-        if (lane == 0) { out_len[unit] = 0; status[unit] = f.st; }
-        return;
+    if constexpr (FRAMED) {
+        const FramedUnit f = framed_parse(src, nbytes, lane);
+        const uint32_t route = framed_route<true>(f);
+        if (route == kFrFail) {
+            if (lane == 0) { out_len[unit] = 0; status[unit] = f.st; }
+            return;
+        }
+        if (route == kFrWalk) return;  // encode_cxx_long_kernel's
+    } else {
+        if (!valid) {
+            if (lane == 0) { out_len[unit] = 0; status[unit] = (reinterpret_cast<uintptr_t>(src) & 7) ? ST_ARG : ST_SIZE; }
+            return;
+        }
+        if ((nbytes >> 3) > kEncMaxWords) return;  // encode_cxx_long_kernel's
     }
-    if (route == kFrWalk) return;  // encode_framed_cxx_walk_kernel's
     uint64_t ob = 0, cap = 0;
     if (WRITE) {
         ob = out_off[unit];
@@ -1384,20 +1292,22 @@ __global__ __launch_bounds__(kBlock) void encode_framed_cxx_kernel(const uint8_t
     }
 }
 
-// The kFrWalk units of the slot call (multi-segment units, and units of more than one tile),
-// piece by piece, a wave each. They may be most of a batch, so a wave looks at kFramedGroup
-// units per step (a lane each: a superset of kFrWalk by the lengths and word 0's low half, the
-// count - 1) and the grid is sized by that; framed_parse and framed_route then decide.
+// The units of more than one tile (encode_cxx_long_unit), found by a small grid that strides
+// over the batch's lengths, 64 per load, and coded a wave each, tile by tile.
+// FRAMED: the kFrWalk units (multi-segment units, and units of more than one tile), piece by
+// piece, a wave each. They may be most of a batch, so a wave looks at kFramedGroup units per
+// step (a lane each: a superset of kFrWalk by the lengths and word 0's low half, the count - 1)
+// and the grid is sized by that; framed_parse and framed_route then decide.
 constexpr uint32_t kFramedGroup = 4;
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void encode_framed_cxx_walk_kernel(const uint8_t* __restrict__ in,
-                                                                        const uint64_t* __restrict__ in_off,
-                                                                        const uint64_t* __restrict__ in_len,
-                                                                        uint32_t n, uint8_t* __restrict__ out,
-                                                                        const uint64_t* __restrict__ out_off,
-                                                                        const uint64_t* __restrict__ out_cap,
-                                                                        uint64_t* __restrict__ out_len,
-                                                                        int32_t* __restrict__ status) {
+template <bool WRITE, bool FRAMED>
+__global__ __launch_bounds__(kBlock) void encode_cxx_long_kernel(const uint8_t* __restrict__ in,
+                                                                 const uint64_t* __restrict__ in_off,
+                                                                 const uint64_t* __restrict__ in_len, uint32_t n,
+                                                                 uint8_t* __restrict__ out,
+                                                                 const uint64_t* __restrict__ out_off,
+                                                                 const uint64_t* __restrict__ out_cap,
+                                                                 uint64_t* __restrict__ out_len,
+                                                                 int32_t* __restrict__ status) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
     __shared__ __attribute__((aligned(16))) uint64_t lut[256];
     const uint32_t lane = lane_id();
@@ -1407,34 +1317,66 @@ __global__ __launch_bounds__(kBlock) void encode_framed_cxx_walk_kernel(const ui
         __syncthreads();
     }
     uint8_t* lds = smem + wave * kEncLds;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kFramedGroup;
-    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kFramedGroup; ubase < n; ubase += stride) {
+    constexpr uint32_t kGroup = FRAMED ? kFramedGroup : kWave;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kGroup;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kGroup; ubase < n; ubase += stride) {
         const uint64_t u = ubase + lane;
-        bool mine = false;
-        if (u < n && lane < kFramedGroup) {
-            const uint64_t len = in_len[u];
-            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
-                   (len >> 3) <= 0xFFFFF000ull &&
-                   ((len >> 3) > kEncMaxWords || (uint32_t)gload64(in + in_off[u]) != 0);
+        uint64_t todo;
+        if constexpr (FRAMED) {
+            bool mine = false;
+            if (u < n && lane < kGroup) {
+                const uint64_t len = in_len[u];
+                mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
+                       (len >> 3) <= 0xFFFFF000ull &&
+                       ((len >> 3) > kEncMaxWords || (uint32_t)gload64(in + in_off[u]) != 0);
+            }
+            todo = __ballot(mine);
+        } else {
+            todo = __ballot(u < n && encode_cxx_long_unit(in, in_off[u < n ? u : 0], in_len[u < n ? u : 0]));
         }
-        uint64_t todo = __ballot(mine);
         while (todo) {  // wave-uniform
             const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
             todo &= todo - 1;
-            const uint8_t* const src = in + framed_uniform64(in_off[unit]);
-            const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
-            if (framed_route<true>(f) != kFrWalk) continue;
             uint64_t ob = 0, cap = 0;
-            if (WRITE) {
-                ob = out_off[unit];
-                cap = out_cap[unit];
-            }
-            uint64_t pos = 0;
-            bool fits = true;
-            framed_walk_cxx<WRITE>(lds, lut, lane, src, f, out + ob, cap, pos, fits);
-            if (lane == 0) {
-                out_len[unit] = pos;
-                status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+            if constexpr (FRAMED) {
+                const uint8_t* const src = in + framed_uniform64(in_off[unit]);
+                const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
+                if (framed_route<true>(f) != kFrWalk) continue;
+                if (WRITE) {
+                    ob = out_off[unit];
+                    cap = out_cap[unit];
+                }
+                uint64_t pos = 0;
+                bool fits = true;
+                framed_walk_cxx<WRITE>(lds, lut, lane, src, f, out + ob, cap, pos, fits);
+                if (lane == 0) {
+                    out_len[unit] = pos;
+                    status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+                }
+            } else {
+                const uint8_t* const src = in + in_off[unit];
+                const uint64_t nwords = in_len[unit] >> 3;
+                if (WRITE) {
+                    ob = out_off[unit];
+                    cap = out_cap[unit];
+                }
+                uint64_t pos = 0;
+                bool fits = true;
+                if (nwords > 0xFFFFF000ull) {  // word indices are u32: one lane
+                    if (lane == 0) {
+                        pos = serial_pack_cxx(src, nwords, nullptr);
+                        if (WRITE) {
+                            fits = pos <= cap;
+                            if (fits) serial_pack_cxx(src, nwords, out + ob);
+                        }
+                    }
+                } else {
+                    encode_piece_cxx<WRITE>(lds, lut, lane, src, (uint32_t)nwords, out + ob, cap, pos, fits);
+                }
+                if (lane == 0) {
+                    out_len[unit] = pos;
+                    status[unit] = (WRITE && !fits) ? ST_SPACE : ST_OK;
+                }
             }
         }
     }
@@ -1764,7 +1706,11 @@ __device__ __forceinline__ void dense_tile(const uint8_t* __restrict__ in, const
 // encode_dense_kernel gave them (status OK: the unit fits below out_cap). A small grid strides
 // over the batch's lengths, 64 per load, as encode_cxx_long_kernel does; a long unit is one
 // wave's work and its input is read twice.
-template <bool WRITE, bool CXX>
+// FRAMED: the units framed_route sends here (kFrWalk: multi-segment units under the C++ rule
+// too, so they may be most of a batch), kFramedGroup per wave and step, not 64, with the grid
+// sized by that (launch_encode_dense). The lane-wise filter is a superset of kFrWalk (word 0's
+// low half is the count - 1); framed_parse and framed_route then decide, as in dense_tile.
+template <bool WRITE, bool CXX, bool FRAMED>
 __global__ __launch_bounds__(kBlock) void encode_dense_long_kernel(const uint8_t* __restrict__ in,
                                                                    const uint64_t* __restrict__ in_off,
                                                                    const uint64_t* __restrict__ in_len, uint32_t n,
@@ -1785,88 +1731,53 @@ __global__ __launch_bounds__(kBlock) void encode_dense_long_kernel(const uint8_t
             ws[i] = 0;
     }
     uint8_t* lds = smem + wave * kEncLds;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kWave;
-    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kWave; ubase < n; ubase += stride) {
+    constexpr uint32_t kGroup = FRAMED ? kFramedGroup : kWave;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kGroup;
+    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kGroup; ubase < n; ubase += stride) {
         const uint64_t u = ubase + lane;
         bool mine = false;
-        if (u < n) {
-            const uint64_t len = in_len[u];
-            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && (len >> 3) > kEncMaxWords &&
-                   (len >> 3) <= 0xFFFFF000ull;
-            if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
-        }
-        uint64_t todo = __ballot(mine);
-        while (todo) {  // wave-uniform
-            const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
-            todo &= todo - 1;
-            const uint8_t* const src = in + in_off[unit];
-            const uint32_t words = (uint32_t)(in_len[unit] >> 3);
-            uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
-            uint64_t pos = 0;
-            if (CXX) {
-                bool fits = true;
-                encode_piece_cxx<WRITE>(lds, lut, lane, src, words, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
-            } else {
-                pos = dense_long_zig<WRITE>(lds, lut, lane, src, words, dst);
+        if constexpr (FRAMED) {
+            if (u < n && lane < kGroup) {
+                const uint64_t len = in_len[u];
+                mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
+                       (len >> 3) <= 0xFFFFF000ull &&
+                       ((len >> 3) > kEncMaxWords || (CXX && (uint32_t)gload64(in + in_off[u]) != 0));
+                if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
             }
-            if (!WRITE && lane == 0) out_len[unit] = pos;
-        }
-    }
-}
-
-// The same two passes over framed messages: the units framed_route sends here (kFrWalk:
-// multi-segment units under the C++ rule too, so they may be most of a batch). A wave looks at
-// kFramedGroup units per step, not 64, and the grid is sized by that (launch_encode_dense), so
-// a batch of walked units does not run 64 to a wave. The lane-wise filter is a superset of
-// kFrWalk (word 0's low half is the count - 1); framed_parse and framed_route then decide, as in
-// encode_framed_dense_kernel. (A kernel of its own, not a template mode of the one above: that
-// one's code stays as it is.)
-template <bool WRITE, bool CXX>
-__global__ __launch_bounds__(kBlock) void encode_framed_dense_long_kernel(const uint8_t* __restrict__ in,
-                                                                          const uint64_t* __restrict__ in_off,
-                                                                          const uint64_t* __restrict__ in_len,
-                                                                          uint32_t n, uint8_t* out,
-                                                                          const uint64_t* out_off, uint64_t* out_len,
-                                                                          const int32_t* status, uint64_t* ws,
-                                                                          uint64_t ws_words) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[kWavesPerBlock * kEncLds];
-    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
-    const uint32_t lane = lane_id();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (WRITE) {
-        lut[threadIdx.x] = compact_selector(threadIdx.x);
-        __syncthreads();
-    } else {
-        // the launch ahead of encode_framed_dense_kernel zeroes its workspace, as above
-        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ws_words; i += (uint64_t)gridDim.x * kBlock)
-            ws[i] = 0;
-    }
-    uint8_t* lds = smem + wave * kEncLds;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock * kFramedGroup;
-    for (uint64_t ubase = (uint64_t)(blockIdx.x * kWavesPerBlock + wave) * kFramedGroup; ubase < n; ubase += stride) {
-        const uint64_t u = ubase + lane;
-        bool mine = false;
-        if (u < n && lane < kFramedGroup) {
-            const uint64_t len = in_len[u];
-            mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && len >= 8 &&
-                   (len >> 3) <= 0xFFFFF000ull &&
-                   ((len >> 3) > kEncMaxWords || (CXX && (uint32_t)gload64(in + in_off[u]) != 0));
-            if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
+        } else {
+            if (u < n) {
+                const uint64_t len = in_len[u];
+                mine = !(reinterpret_cast<uintptr_t>(in + in_off[u]) & 7) && !(len & 7) && (len >> 3) > kEncMaxWords &&
+                       (len >> 3) <= 0xFFFFF000ull;
+                if (WRITE) mine = mine && status[u] == ST_OK && out_len[u] != 0;
+            }
         }
         uint64_t todo = __ballot(mine);
         while (todo) {  // wave-uniform
             const uint32_t unit = (uint32_t)ubase + (uint32_t)__builtin_ctzll(todo);
             todo &= todo - 1;
-            const uint8_t* const src = in + framed_uniform64(in_off[unit]);
-            const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
-            if (framed_route<CXX>(f) != kFrWalk) continue;
-            uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
             uint64_t pos = 0;
-            if (CXX) {
-                bool fits = true;
-                framed_walk_cxx<WRITE>(lds, lut, lane, src, f, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
+            if constexpr (FRAMED) {
+                const uint8_t* const src = in + framed_uniform64(in_off[unit]);
+                const FramedUnit f = framed_parse(src, framed_uniform64(in_len[unit]), lane);
+                if (framed_route<CXX>(f) != kFrWalk) continue;
+                uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
+                if (CXX) {
+                    bool fits = true;
+                    framed_walk_cxx<WRITE>(lds, lut, lane, src, f, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
+                } else {
+                    pos = dense_long_zig<WRITE>(lds, lut, lane, src, f.words, dst);
+                }
             } else {
-                pos = dense_long_zig<WRITE>(lds, lut, lane, src, f.words, dst);
+                const uint8_t* const src = in + in_off[unit];
+                const uint32_t words = (uint32_t)(in_len[unit] >> 3);
+                uint8_t* const dst = WRITE ? out + out_off[unit] : nullptr;
+                if (CXX) {
+                    bool fits = true;
+                    encode_piece_cxx<WRITE>(lds, lut, lane, src, words, dst, WRITE ? out_len[unit] : 0ull, pos, fits);
+                } else {
+                    pos = dense_long_zig<WRITE>(lds, lut, lane, src, words, dst);
+                }
             }
             if (!WRITE && lane == 0) out_len[unit] = pos;
         }
@@ -1875,9 +1786,10 @@ __global__ __launch_bounds__(kBlock) void encode_framed_dense_long_kernel(const 
 
 // Register target: 16 waves are one workgroup per CU (82 KB of LDS), 4 waves per SIMD. (With 8
 // waves the LDS admits three workgroups per CU, 80 VGPRs: the Zig tile fits that, the C++ tile,
-// 95 VGPRs as it comes, does not and runs at two.)
-template <bool WRITE, bool CXX>
-__global__ __launch_bounds__(kDnBlock, (CXX || kDnWaves > 8) ? 4 : 6) void encode_dense_kernel(const uint8_t* __restrict__ in,
+// 95 VGPRs as it comes, does not and runs at two.) FRAMED is dense_tile's FRAMED mode: the same
+// over framed messages, at the 4-waves target whatever kDnWaves is.
+template <bool WRITE, bool CXX, bool FRAMED>
+__global__ __launch_bounds__(kDnBlock, (FRAMED || CXX || kDnWaves > 8) ? 4 : 6) void encode_dense_kernel(const uint8_t* __restrict__ in,
                                                                 const uint64_t* __restrict__ in_off,
                                                                 const uint64_t* __restrict__ in_len, uint32_t n,
                                                                 uint8_t* out, uint64_t out_base, uint64_t out_cap,
@@ -1917,53 +1829,7 @@ __global__ __launch_bounds__(kDnBlock, (CXX || kDnWaves > 8) ? 4 : 6) void encod
     const uint64_t unit = (uint64_t)ticket * kDnWaves + wave;
     du.live = unit < n;
     du.unit = du.live ? (uint32_t)unit : 0u;
-    dense_tile<WRITE, CXX>(in, in_off, in_len, lds, lut, du);
-}
-
-// The same over framed messages (dense_tile's FRAMED mode), with the same register target. (A
-// kernel of its own: encode_dense_kernel's code stays as it is.)
-template <bool WRITE, bool CXX>
-__global__ __launch_bounds__(kDnBlock, 4) void encode_framed_dense_kernel(const uint8_t* __restrict__ in,
-                                                                const uint64_t* __restrict__ in_off,
-                                                                const uint64_t* __restrict__ in_len, uint32_t n,
-                                                                uint8_t* out, uint64_t out_base, uint64_t out_cap,
-                                                                uint64_t* out_off, uint64_t* out_len,
-                                                                int32_t* status, uint64_t* ws_) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[kDnWaves * kEncLds];
-    __shared__ __attribute__((aligned(16))) uint64_t lut[256];
-    __shared__ __attribute__((aligned(16))) uint64_t sx[2 * kDnWaves + 2];
-    dn_gu64* const ws = reinterpret_cast<dn_gu64*>(reinterpret_cast<uintptr_t>(ws_));
-    const uint32_t lane = lane_id();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x == 0)
-        sx[2 * kDnWaves + 1] = __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>(ws),
-                                                      1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (WRITE && threadIdx.x < 256) lut[threadIdx.x] = compact_selector(threadIdx.x);
-    __syncthreads();
-    const uint32_t ticket = __builtin_amdgcn_readfirstlane((uint32_t)sx[2 * kDnWaves + 1]);
-    const uint32_t ntiles = (uint32_t)dense_tiles(n);
-    DenseUnit du;
-    du.sx = sx;
-    du.ws = ws;
-    du.out = out;
-    du.out_base = out_base;
-    du.out_cap = out_cap;
-    du.out_off = out_off;
-    du.out_len = out_len;
-    du.status = status;
-    du.ntiles = ntiles;
-    du.n = n;
-    du.wave = wave;
-    du.lane = lane;
-    du.write = WRITE;
-    du.off = 0;
-    uint8_t* const lds = smem + wave * kEncLds;
-    if (ticket >= ntiles) return;  // block-uniform (the grid is ntiles workgroups: never)
-    du.tile = ticket;
-    const uint64_t unit = (uint64_t)ticket * kDnWaves + wave;
-    du.live = unit < n;
-    du.unit = du.live ? (uint32_t)unit : 0u;
-    dense_tile<WRITE, CXX, true>(in, in_off, in_len, lds, lut, du);
+    dense_tile<WRITE, CXX, FRAMED>(in, in_off, in_len, lds, lut, du);
 }
 
 __global__ void store_u64_kernel(uint64_t* p, uint64_t v) { *p = v; }
@@ -6049,23 +5915,40 @@ hipError_t launch_encode_one(const uint8_t* in, const uint64_t* in_off, const ui
     return hipGetLastError();
 }
 
+// The grid of encode_cxx_long_kernel / encode_dense_long_kernel, which stride over the batch's
+// lengths: 64 units per wave and load. Framed, the walked units may be most of the batch: every
+// wave takes kFramedGroup units a step, up to a grid a few times the resident one.
+static uint32_t long_unit_blocks(uint32_t n, bool framed) {
+    const uint64_t per_block = (uint64_t)kWavesPerBlock * (framed ? kFramedGroup : kWave);
+    return (uint32_t)std::min<uint64_t>(((uint64_t)n + per_block - 1) / per_block, framed ? 4096 : 2048);
+}
+static size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 // The C++ dialect's encoders: a wave per unit (one-tile units, then the longer
-// ones) / per message; no class pass, no side stream and no workspace.
+// ones) / per message; no class pass, no side stream and no workspace. Framed,
+// the same two: the verdicts and the one-tile single-segment units, then the walked units.
+static hipError_t launch_encode_cxx_units(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                          uint32_t n, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap,
+                                          uint64_t* out_len, int32_t* status, bool write, bool framed,
+                                          hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
+    const uint32_t long_blocks = long_unit_blocks(n, framed);
+    with_bool(framed, [&](auto f) {
+        with_bool(write, [&](auto w) {
+            constexpr bool W = decltype(w)::value, F = decltype(f)::value;
+            encode_cxx_kernel<W, F><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
+                                                                   out_len, status);
+            encode_cxx_long_kernel<W, F><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off,
+                                                                             out_cap, out_len, status);
+        });
+    });
+    return hipGetLastError();
+}
 hipError_t launch_encode_cxx(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                              uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
                              int32_t* status, bool write, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
-    // the units of more than one tile: a grid striding over the lengths, 64 per wave and load
-    const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
-    with_bool(write, [&](auto w) {
-        constexpr bool W = decltype(w)::value;
-        encode_cxx_kernel<W><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap, out_len,
-                                                            status);
-        encode_cxx_long_kernel<W><<<long_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                      out_len, status);
-    });
-    return hipGetLastError();
+    return launch_encode_cxx_units(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, write, false, stream);
 }
 
 hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* seg_len, const uint32_t* seg_first,
@@ -6082,37 +5965,25 @@ hipError_t launch_encode_message_cxx(const uint64_t* seg_ptr, const uint64_t* se
 }
 
 // Framed messages into slots (capnp_packed_encode_framed_batch). The C++
-// dialect is two kernels: the verdicts and the one-tile single-segment units, then the walked units. The Zig dialect is launch_encode over the effective
+// dialect is launch_encode_cxx_units. The Zig dialect is launch_encode over the effective
 // lengths a check kernel leaves in the workspace (0 for a failed unit, whose slot then stays
 // untouched), and the failed units' verdicts put in place after it. The workspace: the class
 // workspace launch_encode takes, then n u64 lengths, then n i32 verdicts, each part 256-B aligned.
-static size_t framed_round256(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t framed_workspace_bytes(uint32_t n) {
-    return framed_round256(queue_bytes(n)) + framed_round256(8 * (size_t)n) + framed_round256(4 * (size_t)n);
+    return round256(queue_bytes(n)) + round256(8 * (size_t)n) + round256(4 * (size_t)n);
 }
 
 hipError_t launch_encode_framed(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                 uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
                                 int32_t* status, bool write, bool cxx, void* ws, hipStream_t stream) {
+    if (cxx)
+        return launch_encode_cxx_units(in, in_off, in_len, n, out, out_off, out_cap, out_len, status, write, true, stream);
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)n + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (cxx) {
-        // the walked units: a grid of kFramedGroup units a wave and step, up to a few times the resident one
-        const uint64_t per_block = (uint64_t)kWavesPerBlock * kFramedGroup;
-        const uint32_t walk_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + per_block - 1) / per_block, 4096);
-        with_bool(write, [&](auto w) {
-            constexpr bool W = decltype(w)::value;
-            encode_framed_cxx_kernel<W><<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off, out_cap,
-                                                                       out_len, status);
-            encode_framed_cxx_walk_kernel<W><<<walk_blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, out, out_off,
-                                                                                 out_cap, out_len, status);
-        });
-        return hipGetLastError();
-    }
     uint8_t* const w8 = static_cast<uint8_t*>(ws);
-    const size_t qb = framed_round256(queue_bytes(n));
+    const size_t qb = round256(queue_bytes(n));
     uint64_t* const eff_len = reinterpret_cast<uint64_t*>(w8 + qb);
-    int32_t* const verdict = reinterpret_cast<int32_t*>(w8 + qb + framed_round256(8 * (size_t)n));
+    int32_t* const verdict = reinterpret_cast<int32_t*>(w8 + qb + round256(8 * (size_t)n));
     framed_check_kernel<<<blocks, kBlock, 0, stream>>>(in, in_off, in_len, n, eff_len, verdict);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -6126,10 +5997,7 @@ hipError_t launch_encode_framed(const uint8_t* in, const uint64_t* in_off, const
 // zeroed on every call, ahead of the launch, by the long units' size pass (the whole workspace,
 // a multiple of 256 bytes). Not by hipMemsetAsync: captured by torch.cuda.graph, its node
 // filled the workspace with a stray 16-byte pattern on replay (ROCm 7.2).
-size_t dense_workspace_bytes(uint32_t n) {
-    const size_t bytes = 8 * ((size_t)kDnHead + (size_t)dense_tiles(n));
-    return (bytes + 255) & ~(size_t)255;
-}
+size_t dense_workspace_bytes(uint32_t n) { return round256(8 * ((size_t)kDnHead + (size_t)dense_tiles(n))); }
 
 hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                                uint8_t* out, uint64_t out_base, uint64_t out_cap, uint64_t* out_off,
@@ -6142,41 +6010,23 @@ hipError_t launch_encode_dense(const uint8_t* in, const uint64_t* in_off, const 
     }
     const uint32_t blocks = (uint32_t)dense_tiles(n);
     uint64_t* const w64 = static_cast<uint64_t*>(ws);
-    // the units of more than one tile: their sizes before, their bytes after (no such unit: one
-    // pass over the lengths each)
-    const uint32_t long_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, 2048);
-    if (framed) {
-        // framed messages: the walked units may be most of the batch, so the long grid gives every
-        // wave kFramedGroup units a step (up to a grid a few times the resident one)
-        const uint64_t per_block = (uint64_t)kWavesPerBlock * kFramedGroup;
-        const uint32_t walk_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + per_block - 1) / per_block, 4096);
-        with_bool(cxx, [&](auto c) {
-            constexpr bool C = decltype(c)::value;
+    // the units of more than one tile (framed: the walked units): their sizes before, their bytes
+    // after (no such unit: one pass over the lengths each)
+    const uint32_t long_blocks = long_unit_blocks(n, framed);
+    with_bool(cxx, [&](auto c) {
+        with_bool(framed, [&](auto f) {
+            constexpr bool C = decltype(c)::value, F = decltype(f)::value;
             const auto dense_long = [&](auto w) {
-                encode_framed_dense_long_kernel<decltype(w)::value, C><<<walk_blocks, kBlock, 0, stream>>>(
+                encode_dense_long_kernel<decltype(w)::value, C, F><<<long_blocks, kBlock, 0, stream>>>(
                     in, in_off, in_len, n, out, out_off, out_len, status, w64, dense_workspace_bytes(n) / 8);
             };
             dense_long(std::false_type{});
             with_bool(out != nullptr, [&](auto w) {
-                encode_framed_dense_kernel<decltype(w)::value, C><<<blocks, kDnBlock, 0, stream>>>(
+                encode_dense_kernel<decltype(w)::value, C, F><<<blocks, kDnBlock, 0, stream>>>(
                     in, in_off, in_len, n, out, out_base, out_cap, out_off, out_len, status, w64);
             });
             if (out) dense_long(std::true_type{});
         });
-        return hipGetLastError();
-    }
-    with_bool(cxx, [&](auto c) {
-        constexpr bool C = decltype(c)::value;
-        const auto dense_long = [&](auto w) {
-            encode_dense_long_kernel<decltype(w)::value, C><<<long_blocks, kBlock, 0, stream>>>(
-                in, in_off, in_len, n, out, out_off, out_len, status, w64, dense_workspace_bytes(n) / 8);
-        };
-        dense_long(std::false_type{});
-        with_bool(out != nullptr, [&](auto w) {
-            encode_dense_kernel<decltype(w)::value, C><<<blocks, kDnBlock, 0, stream>>>(
-                in, in_off, in_len, n, out, out_base, out_cap, out_off, out_len, status, w64);
-        });
-        if (out) dense_long(std::true_type{});
     });
     return hipGetLastError();
 }
