@@ -214,6 +214,10 @@ SIGNATURES = {
                                                        _vp, _vp, _vp]),
     "capnp_packed_validate_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64,
                                                    ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp]),
+    "capnp_packed_read_fields_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp,
+                                                      _vp, _vp, _vp]),
+    "capnp_packed_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64, _vp,
+                                                 _vp]),
     "capnp_packed_scan_scratch_bytes": (_sz, [ctypes.c_uint32]),
     "capnp_packed_lengths_to_offsets": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp,
                                                        _sz, _vp]),
@@ -482,9 +486,112 @@ class Message:
         _raise(int(st.item()), "Message.validate")
         return int(words.item())
 
+    def get_root_struct(self, device="cuda") -> "StructReader":
+        """message.zig:973-985 getRootStruct, resolved on the device (one n = 1
+        read_fields_batch call); raises the reference's error."""
+        if len(self.segments) == 0:
+            raise EmptyMessage("Message.getRootStruct: no segments")
+        root = StructReader(self, (), device)
+        root._read(FIELD_U8, 0)  # resolves the root: its errors are getRootStruct's
+        return root
+
     def deinit(self) -> None:
         self.segments = []
         self.backing_data = None
+
+
+class StructReader:
+    """Mirror of StructReader (message.zig:1010-1443): the schema-less reads of a struct reached
+    from the root by readStruct steps. Every read is one n = 1 capnp_packed_read_fields_batch
+    call on the device over the message's framed bytes (slices: plus one gather_batch) and
+    raises the reference's error; there is no CPU path."""
+
+    def __init__(self, message: Message, path, device):
+        self.message, self.path, self.device = message, tuple(path), device
+        self._dev = None
+
+    def _framed(self):
+        if self._dev is None:
+            framed = np.frombuffer(frame_segments(self.message.segments), dtype=np.uint8)
+            self._dev = (torch.from_numpy(framed.copy()).to(self.device),
+                         torch.zeros(1, dtype=torch.int64, device=self.device),
+                         torch.full((1,), framed.size, dtype=torch.int64, device=self.device))
+        return self._dev
+
+    def _read(self, kind, offset, bit=0, what="StructReader"):
+        d_in, off, ln = self._framed()
+        out = torch.zeros(3, dtype=torch.int64, device=self.device)
+        st = torch.full((1,), -1, dtype=torch.int32, device=self.device)
+        read_fields_batch(d_in, off, ln, [Field(kind, offset, bit, self.path)], out[0:1], out[1:2], st, out[2:3])
+        _raise(int(st.item()), what)
+        v, l, c = (int(x) for x in out.cpu().numpy().view(np.uint64))
+        return v, l, c
+
+    def _slice(self, kind, index, what) -> tuple:
+        v, l, c = self._read(kind, index, what=what)
+        d_in = self._framed()[0]
+        dst = torch.empty(l, dtype=torch.uint8, device=self.device)
+        st = torch.full((1,), -1, dtype=torch.int32, device=self.device)
+        gather_batch(d_in, torch.tensor([v], dtype=torch.int64, device=self.device),
+                     torch.tensor([l], dtype=torch.int64, device=self.device), dst,
+                     torch.zeros(1, dtype=torch.int64, device=self.device), st, cap=l)
+        _raise(int(st.item()), what)
+        return dst.cpu().numpy().tobytes(), c
+
+    def read_u8(self, byte_offset: int) -> int:
+        return self._read(FIELD_U8, byte_offset)[0]
+
+    def read_u16(self, byte_offset: int) -> int:
+        return self._read(FIELD_U16, byte_offset)[0]
+
+    def read_u32(self, byte_offset: int) -> int:
+        return self._read(FIELD_U32, byte_offset)[0]
+
+    def read_u64(self, byte_offset: int) -> int:
+        return self._read(FIELD_U64, byte_offset)[0]
+
+    def read_bool(self, byte_offset: int, bit_offset: int) -> bool:
+        return bool(self._read(FIELD_BOOL, byte_offset, bit_offset)[0])
+
+    def read_union_discriminant(self, byte_offset: int) -> int:
+        return self.read_u16(byte_offset)
+
+    def read_text(self, pointer_index: int) -> bytes:
+        return self._slice(FIELD_TEXT, pointer_index, "StructReader.readText")[0]
+
+    def read_data(self, pointer_index: int) -> bytes:
+        return self._slice(FIELD_DATA, pointer_index, "StructReader.readData")[0]
+
+    def _list(self, kind, index, dtype, what) -> list:
+        raw, count = self._slice(kind, index, what)
+        return np.frombuffer(raw, dtype=dtype)[:count].tolist()
+
+    def read_u16_list(self, pointer_index: int) -> list:
+        return self._list(FIELD_LIST_16, pointer_index, "<u2", "StructReader.readU16List")
+
+    def read_u32_list(self, pointer_index: int) -> list:
+        return self._list(FIELD_LIST_32, pointer_index, "<u4", "StructReader.readU32List")
+
+    def read_u64_list(self, pointer_index: int) -> list:
+        return self._list(FIELD_LIST_64, pointer_index, "<u8", "StructReader.readU64List")
+
+    def read_f32_list(self, pointer_index: int) -> list:
+        return self._list(FIELD_LIST_32, pointer_index, "<f4", "StructReader.readF32List")
+
+    def read_f64_list(self, pointer_index: int) -> list:
+        return self._list(FIELD_LIST_64, pointer_index, "<f8", "StructReader.readF64List")
+
+    def read_bool_list(self, pointer_index: int) -> list:
+        raw, count = self._slice(FIELD_LIST_BIT, pointer_index, "StructReader.readBoolList")
+        return [bool((raw[i >> 3] >> (i & 7)) & 1) for i in range(count)]
+
+    def read_struct(self, pointer_index: int) -> "StructReader":
+        """readStruct (:1224-1235). The device descriptor holds four steps from the root: a fifth
+        raises InvalidArgument."""
+        child = StructReader(self.message, self.path + (pointer_index,), self.device)
+        child._dev = self._dev
+        child._read(FIELD_U8, 0, what="StructReader.readStruct")
+        return child
 
 
 class Reader:
@@ -1314,6 +1421,68 @@ def validate_batch(d_in, in_off, in_len, status, words=None, segment_count_limit
     _raise(lib().capnp_packed_validate_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, segment_count_limit,
                                              traversal_limit_words, nesting_limit, _ptr(status), _ptr(words),
                                              _stream(stream)), "validate_batch")
+
+
+# capnp_packed_read_fields_batch kinds (include/capnp_packed.h)
+FIELD_U8, FIELD_U16, FIELD_U32, FIELD_U64, FIELD_BOOL = 0, 1, 2, 3, 4
+FIELD_TEXT, FIELD_DATA, FIELD_LIST_BIT, FIELD_LIST_16, FIELD_LIST_32, FIELD_LIST_64 = 5, 6, 7, 8, 9, 10
+MAX_FIELDS = 32
+MAX_PATH = 4
+
+
+class CField(ctypes.Structure):
+    """struct capnp_packed_field"""
+    _fields_ = [("kind", ctypes.c_uint32), ("offset", ctypes.c_uint32), ("bit", ctypes.c_uint32),
+                ("path_len", ctypes.c_uint32), ("path", ctypes.c_uint32 * 4)]
+
+
+class Field:
+    """One column of read_fields_batch: a kind, a byte offset in the data section (data kinds) or
+    a pointer index (slice kinds), BOOL's bit, and the pointer indices of the readStruct steps
+    from the root to the struct the field is read from."""
+
+    def __init__(self, kind: int, offset: int, bit: int = 0, path=()):
+        self.kind, self.offset, self.bit, self.path = int(kind), int(offset), int(bit), tuple(int(p) for p in path)
+
+    def __repr__(self):
+        return f"Field(kind={self.kind}, offset={self.offset}, bit={self.bit}, path={self.path})"
+
+    def c(self) -> CField:
+        # a path longer than the descriptor holds keeps its length, so the library refuses it
+        padded = (self.path + (0,) * MAX_PATH)[:MAX_PATH]
+        return CField(self.kind, self.offset, self.bit, len(self.path), (ctypes.c_uint32 * 4)(*padded))
+
+
+def _cfields(fields):
+    arr = (CField * max(1, len(fields)))()
+    for i, f in enumerate(fields):
+        arr[i] = f.c()
+    return arr
+
+
+def read_fields_batch(d_in, in_off, in_len, fields, value, length, status, count=None, stream=None) -> None:
+    """getRootStruct + StructReader reads (message.zig:973-985, :1010-1443) of a batch of framed
+    messages as columns: entry f * n + i of value / length / count (int64) and status (int32) is
+    field f of message i. A slice kind's value is the content's byte offset from d_in, so
+    (value, length) columns feed gather_batch unchanged."""
+    n = _units(in_off, in_len)
+    nf = len(fields)
+    for t in (value, length, status, count):
+        if t is not None and t.numel() < n * nf:
+            raise InvalidArgument(f"field-major output has {t.numel()} entries for {nf} fields x {n} messages")
+    arr = _cfields(fields)  # read by the call itself (passed to the kernel by value): free after it
+    _raise(lib().capnp_packed_read_fields_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n,
+                                                ctypes.addressof(arr), nf, _ptr(value), _ptr(length),
+                                                _ptr(count), _ptr(status), _stream(stream)), "read_fields_batch")
+
+
+def gather_batch(d_in, src_off, src_len, d_out, dst_off, status, cap=None, stream=None) -> None:
+    """Row i = d_in[src_off[i] : src_off[i] + src_len[i]] copied to d_out[dst_off[i]:], byte-exact
+    at any alignment; a row that would end past cap (default: d_out's size) gets OUT_OF_SPACE."""
+    n = _units(src_off, src_len, dst_off, status)
+    cap = d_out.numel() * d_out.element_size() if cap is None else int(cap)
+    _raise(lib().capnp_packed_gather_batch(_ptr(d_in), _ptr(src_off), _ptr(src_len), n, _ptr(d_out), _ptr(dst_off),
+                                           cap, _ptr(status), _stream(stream)), "gather_batch")
 
 
 def lengths_to_offsets(lengths, base: int = 0, out=None, stream=None):

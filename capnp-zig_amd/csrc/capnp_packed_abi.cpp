@@ -870,6 +870,41 @@ int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
                     "validate launch");
 }
 
+int capnp_packed_read_fields_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                   uint32_t n, const capnp_packed_field* fields, uint32_t n_fields,
+                                   uint64_t* d_value, uint64_t* d_len, uint64_t* d_count, int32_t* d_status,
+                                   void* stream) {
+    if (n_fields > CAPNP_PACKED_MAX_FIELDS) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "more than 32 fields");
+    if (n == 0 || n_fields == 0) return CAPNP_PACKED_OK;
+    if (!fields || !d_in || !d_in_off || !d_in_len || !d_value || !d_len || !d_status)
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    for (uint32_t f = 0; f < n_fields; ++f) {
+        const capnp_packed_field& a = fields[f];
+        if (a.kind > CAPNP_PACKED_FIELD_LIST_64) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown field kind");
+        if (a.bit > (a.kind == CAPNP_PACKED_FIELD_BOOL ? 7u : 0u))
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bit is 0-7 for BOOL and 0 otherwise");
+        if (a.path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
+    }
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_read_fields(d_in, d_in_off, d_in_len, n, fields, n_fields, d_value, d_len, d_count,
+                                            d_status, static_cast<hipStream_t>(stream)),
+                    "read-fields launch");
+}
+
+int capnp_packed_gather_batch(const uint8_t* d_in, const uint64_t* d_src_off, const uint64_t* d_src_len, uint32_t n,
+                              uint8_t* d_out, const uint64_t* d_dst_off, uint64_t out_cap, int32_t* d_status,
+                              void* stream) {
+    if (n == 0) return CAPNP_PACKED_OK;
+    if (!d_src_off || !d_src_len || !d_dst_off || !d_status || (out_cap && (!d_in || !d_out)))
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_gather(d_in, d_src_off, d_src_len, n, d_out, d_dst_off, out_cap, d_status,
+                                       static_cast<hipStream_t>(stream)),
+                    "gather launch");
+}
+
 size_t capnp_packed_scan_scratch_bytes(uint32_t n) { return cpk::scan_scratch_bytes(n); }
 
 int capnp_packed_lengths_to_offsets(const uint64_t* d_len, uint32_t n, uint64_t base, uint64_t* d_off,

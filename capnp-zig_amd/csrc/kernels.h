@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "capnp_packed.h"
+
 namespace cpk {
 
 // Batch encode / decode (write = false: sizes only). ws: optional caller workspace of
@@ -123,6 +125,16 @@ hipError_t launch_message_init(const uint8_t* in, const uint64_t* in_off, const 
 hipError_t launch_validate(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                            uint64_t seg_limit, uint64_t trav_limit, uint32_t nest_limit, int32_t* status,
                            uint64_t* words, hipStream_t stream);
+
+// StructReader's reads over a batch (capnp_packed_read_fields_batch): the
+// descriptors (host memory, checked by the caller, at most CAPNP_PACKED_MAX_FIELDS) go to the
+// kernel by value. launch_gather: the ragged byte copy of capnp_packed_gather_batch.
+hipError_t launch_read_fields(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                              const capnp_packed_field* fields, uint32_t n_fields, uint64_t* value, uint64_t* len,
+                              uint64_t* count, int32_t* status, hipStream_t stream);
+hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint64_t* src_len, uint32_t n,
+                         uint8_t* out, const uint64_t* dst_off, uint64_t out_cap, int32_t* status,
+                         hipStream_t stream);
 
 hipError_t launch_generate(uint8_t* out, uint64_t n_units, uint64_t unit_bytes, uint64_t unit_base,
                            uint64_t seed, uint32_t thr, hipStream_t stream);

@@ -273,6 +273,12 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
     return v;
 }
 
+// a struct / list pointer's signed 30-bit offset in words (Message.validate, the struct reads)
+__device__ __forceinline__ int64_t ptr_offset_words(uint64_t w) {  // message.zig:11-18
+    const uint32_t raw = (uint32_t)((w >> 2) & 0x3FFFFFFFu);
+    return (raw & 0x20000000u) ? (int64_t)raw - ((int64_t)1 << 30) : (int64_t)raw;
+}
+
 // Stage nch 16-B chunks from global g[0 .. 16*nch) into lds[0 .. 16*nch):
 // lane l moves chunks l, l+64, ... Loads AND stores are unconditional, with the
 // chunk index clamped to nch-1 (a clamped lane re-writes the last chunk with the

@@ -4801,11 +4801,6 @@ enum : uint32_t {
     VK_REQ_PTR,  // (no read) issue the read of the next pointer word
 };
 
-__device__ __forceinline__ int64_t ptr_offset_words(uint64_t w) {  // message.zig:11-18
-    const uint32_t raw = (uint32_t)((w >> 2) & 0x3FFFFFFFu);
-    return (raw & 0x20000000u) ? (int64_t)raw - ((int64_t)1 << 30) : (int64_t)raw;
-}
-
 // Deep-path arguments (VdDeep): the list of deferred messages and its count; for the DEEP
 // instance also the global frame stack (frame i of global lane g at [i * lanes + g]) with the
 // frames' nesting values, its depth and the lanes of the grid that take messages.
@@ -5610,6 +5605,7 @@ __global__ __launch_bounds__(kWvBlock) void split_walk_kernel(
 #include "kernels/generate_scan.h"
 // host only: the per-stream side-launch context and the launch policy flags
 #include "kernels/side_launch.h"
+#include "kernels/struct_read.h"
 
 namespace cpk {
 
@@ -6244,6 +6240,30 @@ hipError_t launch_scan(const uint64_t* len, uint32_t n, uint64_t base, uint64_t*
     scan_local_kernel<<<nb, 256, 0, stream>>>(len, n, off, scratch);
     scan_partials_kernel<<<1, 1024, 0, stream>>>(scratch, nb, base, off, n);
     scan_apply_kernel<<<nb, 256, 0, stream>>>(off, n, scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_read_fields(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                              const capnp_packed_field* fields, uint32_t n_fields, uint64_t* value, uint64_t* len,
+                              uint64_t* count, int32_t* status, hipStream_t stream) {
+    SrFields fs{};
+    for (uint32_t f = 0; f < n_fields; ++f) {
+        fs.f[f] = fields[f];
+        const capnp_packed_field& a = fields[f];
+        bool same = f > 0 && a.path_len == fields[f - 1].path_len;
+        for (uint32_t k = 0; same && k < a.path_len; ++k) same = a.path[k] == fields[f - 1].path[k];
+        if (same) fs.same |= 1u << f;
+    }
+    read_fields_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, in_off, in_len, n, fs, n_fields, value,
+                                                                         len, count, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint64_t* src_len, uint32_t n,
+                         uint8_t* out, const uint64_t* dst_off, uint64_t out_cap, int32_t* status,
+                         hipStream_t stream) {
+    gather_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, src_off, src_len, n, out, dst_off, out_cap,
+                                                                    status);
     return hipGetLastError();
 }
 

@@ -53,7 +53,10 @@ extern "C" {
  *     streams of packed messages split into their messages: the reader's half of the above).
  *   2, additions only: capnp_packed_encode_framed, capnp_packed_encode_framed_workspace_bytes,
  *     capnp_packed_encode_framed_batch and capnp_packed_encode_framed_dense_batch (the encoders
- *     over framed messages: under DIALECT_CXX the bytes of capnp convert binary:packed). */
+ *     over framed messages: under DIALECT_CXX the bytes of capnp convert binary:packed).
+ *   2, additions only: capnp_packed_read_fields_batch, capnp_packed_gather_batch, the
+ *     capnp_packed_field descriptor and the CAPNP_PACKED_FIELD_* kinds (the root struct's and
+ *     nested structs' scalar and slice reads as columns, and the slices as dense bytes). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -573,6 +576,103 @@ int capnp_packed_message_init_batch(const uint8_t* d_in, const uint64_t* d_in_of
 int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                 uint32_t n, uint64_t segment_count_limit, uint64_t traversal_limit_words,
                                 uint32_t nesting_limit, int32_t* d_status, uint64_t* d_words, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Reading fields of decoded messages on the device: getRootStruct
+ * (message.zig:973-985), readStruct along a path (:1224-1235) and StructReader's scalar and
+ * slice reads (:1051-1158, :1187-1198, :1259-1443) for n framed messages and n_fields fields
+ * each, as columns. No schema: a field is a byte offset or a pointer index.
+ *   kind        reference read                            offset        value / len / count
+ *   U8..U64     readU8 / readU16 (readUnionDiscriminant)  byte offset   the value zero-extended / its
+ *               / readU32 / readU64                       in the data   width in bytes / 1
+ *   BOOL        readBool(offset, bit)                     section       0 or 1 / 1 / 1
+ *   TEXT        readText                                  pointer       the content's byte offset FROM
+ *   DATA        readData, readU8List (element size 2)     index         d_in / its byte length (bit
+ *   LIST_BIT    readBoolList (1)                                        lists: (count + 7) / 8) / the
+ *   LIST_16/32/64  readU16List / U32 and F32 / U64 and F64 (3, 4, 5)    element count
+ * path: the struct the field is read from is root.readStruct(path[0])...readStruct(path[path_len - 1]).
+ * `fields` is HOST memory and is passed to the kernel by value: no upload and no allocation, the
+ * call is asynchronous on `stream`, keeps no library state and is capturable in a hipGraph.
+ * Outputs are field-major: entry f * n + i is field f of message i, so d_value + f * n is a
+ * column (d_count may be NULL). A failed entry gets value 0, len 0, count 0.
+ * Message i is d_in[d_in_off[i] .. + d_in_len[i]) and starts at a multiple of 8; a misaligned
+ * offset or a length of 4 GiB or more gives INVALID_ARGUMENT for every field of that message.
+ * Per message, in the reference's order (the first error is the status of every field):
+ *   Message.init's table parse, with capnp_packed_message_init_batch's statuses;
+ *   getRootStruct: TRUNCATED_MESSAGE when segment 0 is shorter than 8 bytes (EMPTY_MESSAGE, no
+ *     segments, cannot come out of the table parse: a table lists at least one);
+ *   resolveStructPointer (:492-523) through resolvePointer with depth 8 (:451-490: single-far
+ *     chains, the double-far landing pad and its content override): INVALID_SEGMENT_ID,
+ *     OUT_OF_BOUNDS (a landing pad past its segment), INVALID_FAR_POINTER,
+ *     NESTING_LIMIT_EXCEEDED (an eighth far hop), INVALID_POINTER (null, not a struct pointer, or
+ *     a negative offset), TRUNCATED_MESSAGE (the struct runs past its segment).
+ * Per field: each path step is readStruct: OUT_OF_BOUNDS (index past the pointer section),
+ * INVALID_POINTER (null), then resolveStructPointer as above. Then
+ *   data kinds: a field that does not lie wholly inside the data section
+ *     (offset + width > 8 * data words) reads as the default: value 0, status OK, d_len 0,
+ *     d_count 0 (the reference's schema-evolution rule);
+ *   slice kinds (resolveListPointerAt, resolveListPointer :525-561): OUT_OF_BOUNDS (index past
+ *     the section), INVALID_POINTER (null; not a list after resolution), resolvePointer's errors,
+ *     OUT_OF_BOUNDS (a negative offset, or the content of the list AS ITS POINTER DESCRIBES IT
+ *     runs past its segment), then INVALID_POINTER (the element size is not the kind's);
+ *   TEXT (readText): an index past the section or a null pointer is OK with length 0; one
+ *     trailing NUL byte is dropped from d_len and d_count.
+ * Reference error names without a status of their own: InvalidRootPointer and InvalidTextPointer
+ * are INVALID_POINTER, PointerDepthLimit is NESTING_LIMIT_EXCEEDED; InvalidSegmentId,
+ * OutOfBounds, InvalidFarPointer, InvalidPointer, TruncatedMessage and EmptyMessage keep theirs.
+ * Reads: every load is an aligned 8-byte word of the message's segment table or of one of its
+ * segments (a 4-byte load when the message has fewer than 8 bytes); no byte outside
+ * [off, off + len) is read.
+ * Host-side checks, INVALID_ARGUMENT before any device work: n_fields > CAPNP_PACKED_MAX_FIELDS;
+ * with n > 0 and n_fields > 0, a NULL array (d_count excepted), an unknown kind, bit > 7 or
+ * bit != 0 on a kind other than BOOL, path_len > CAPNP_PACKED_MAX_PATH. n == 0 or n_fields == 0
+ * is OK with no device work. Out of scope: struct and pointer lists, capabilities, XOR defaults,
+ * the *Strict reads, UTF-8 validation.
+ * ------------------------------------------------------------------------ */
+#define CAPNP_PACKED_FIELD_U8 0u       /* readU8 (message.zig:1120) */
+#define CAPNP_PACKED_FIELD_U16 1u      /* readU16 (:1097), readUnionDiscriminant */
+#define CAPNP_PACKED_FIELD_U32 2u      /* readU32 (:1074) */
+#define CAPNP_PACKED_FIELD_U64 3u      /* readU64 (:1051) */
+#define CAPNP_PACKED_FIELD_BOOL 4u     /* readBool (:1143) */
+#define CAPNP_PACKED_FIELD_TEXT 5u     /* readText (:1417) */
+#define CAPNP_PACKED_FIELD_DATA 6u     /* readData / readU8List (:1259, :1270): element size 2 */
+#define CAPNP_PACKED_FIELD_LIST_BIT 7u /* readBoolList: element size 1 */
+#define CAPNP_PACKED_FIELD_LIST_16 8u  /* readU16List: 3 */
+#define CAPNP_PACKED_FIELD_LIST_32 9u  /* readU32List / F32: 4 */
+#define CAPNP_PACKED_FIELD_LIST_64 10u /* readU64List / F64: 5 */
+#define CAPNP_PACKED_MAX_FIELDS 32u
+#define CAPNP_PACKED_MAX_PATH 4u
+typedef struct capnp_packed_field {
+    uint32_t kind;     /* CAPNP_PACKED_FIELD_* */
+    uint32_t offset;   /* data kinds: byte offset in the data section; pointer kinds: pointer index */
+    uint32_t bit;      /* BOOL: 0-7; otherwise 0 */
+    uint32_t path_len; /* 0: the root struct; k: root.readStruct(path[0])...readStruct(path[k-1]) */
+    uint32_t path[4];  /* pointer indices */
+} capnp_packed_field;
+int capnp_packed_read_fields_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                   uint32_t n, const capnp_packed_field* fields /* HOST */, uint32_t n_fields,
+                                   uint64_t* d_value /* n_fields * n */, uint64_t* d_len /* n_fields * n */,
+                                   uint64_t* d_count /* n_fields * n; may be NULL */,
+                                   int32_t* d_status /* n_fields * n */, void* stream);
+
+/* The slices as dense bytes: row i copies d_in[d_src_off[i] .. + d_src_len[i]) to
+ * d_out[d_dst_off[i] ..), both sides at any byte alignment. A d_value / d_len column of
+ * capnp_packed_read_fields_batch passes unchanged as (d_src_off, d_src_len), and
+ * capnp_packed_lengths_to_offsets(d_len) gives dense destination offsets; offsets i * stride
+ * into a zeroed buffer give a padded [n, stride] tensor.
+ * A row that would end past out_cap (d_dst_off[i] + d_src_len[i] > out_cap, the sum taken
+ * without wrapping) is not written and gets OUT_OF_SPACE; every other row is OK, and one of
+ * length 0 touches nothing. Writes are byte-exact: no byte of d_out outside
+ * a row's range is modified, so rows may be packed back to back. Loads are aligned 16-byte
+ * chunks inside the 16-byte lines a row touches (the packed-side rule of every reader here).
+ * Overlapping source and destination ranges are undefined. Asynchronous on `stream`, no
+ * allocation, no library state, capturable in a hipGraph; n == 0 is OK with NULL arrays.
+ * Parallelism: rows of at most 512 bytes are spread over a wave by 16-byte pieces; a longer row
+ * is copied by ONE wave. A batch whose bytes sit in a handful of very long rows therefore runs
+ * on a handful of waves; long rows are not tiled across waves. */
+int capnp_packed_gather_batch(const uint8_t* d_in, const uint64_t* d_src_off, const uint64_t* d_src_len,
+                              uint32_t n, uint8_t* d_out, const uint64_t* d_dst_off, uint64_t out_cap,
+                              int32_t* d_status, void* stream);
 
 /* Exclusive scan of n lengths into n+1 offsets (d_off[0] = base, d_off[n] =
  * base + total), on device.

@@ -135,6 +135,42 @@ pub extern "capnp_packed" fn capnp_packed_validate_batch(
     segment_count_limit: u64, traversal_limit_words: u64, nesting_limit: u32,
     d_status: [*]i32, d_words: ?[*]u64, stream: ?*anyopaque,
 ) c_int;
+/// A field of capnp_packed_read_fields_batch (struct capnp_packed_field): a byte offset in the
+/// data section (data kinds) or a pointer index (slice kinds), read from the struct reached by
+/// root.readStruct(path[0])...readStruct(path[path_len - 1]).
+pub const field_u8: u32 = 0;
+pub const field_u16: u32 = 1;
+pub const field_u32: u32 = 2;
+pub const field_u64: u32 = 3;
+pub const field_bool: u32 = 4;
+pub const field_text: u32 = 5;
+pub const field_data: u32 = 6;
+pub const field_list_bit: u32 = 7;
+pub const field_list_16: u32 = 8;
+pub const field_list_32: u32 = 9;
+pub const field_list_64: u32 = 10;
+pub const max_fields: u32 = 32;
+pub const max_path: u32 = 4;
+pub const Field = extern struct {
+    kind: u32,
+    offset: u32,
+    bit: u32 = 0,
+    path_len: u32 = 0,
+    path: [4]u32 = .{ 0, 0, 0, 0 },
+};
+/// getRootStruct + StructReader's scalar and slice reads (message.zig:973-985, :1010-1443) of n
+/// framed messages as field-major columns; `fields` is host memory (at most max_fields).
+pub extern "capnp_packed" fn capnp_packed_read_fields_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    fields: [*]const Field, n_fields: u32, d_value: [*]u64, d_len: [*]u64, d_count: ?[*]u64,
+    d_status: [*]i32, stream: ?*anyopaque,
+) c_int;
+/// Row i = d_in[d_src_off[i] .. + d_src_len[i]) copied to d_out[d_dst_off[i] ..), byte-exact;
+/// a slice column of the call above passes unchanged as (d_src_off, d_src_len).
+pub extern "capnp_packed" fn capnp_packed_gather_batch(
+    d_in: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, n: u32,
+    d_out: [*]u8, d_dst_off: [*]const u64, out_cap: u64, d_status: [*]i32, stream: ?*anyopaque,
+) c_int;
 /// Class workspace for the *_batch_ws calls (graph-safe batches with no shared state): unit
 /// lists, the long-unit tile / window table and the decoder's piece records (~750 B per unit).
 /// d_ws must be 256-B aligned (hipMalloc's alignment); a misaligned one is InvalidArgument.
