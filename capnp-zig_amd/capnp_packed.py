@@ -218,6 +218,11 @@ SIGNATURES = {
                                                       _vp, _vp, _vp]),
     "capnp_packed_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64, _vp,
                                                  _vp]),
+    "capnp_packed_list_heads_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
+                                                     ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "capnp_packed_read_elements_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                        ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp, _vp]),
     "capnp_packed_scan_scratch_bytes": (_sz, [ctypes.c_uint32]),
     "capnp_packed_lengths_to_offsets": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp,
                                                        _sz, _vp]),
@@ -592,6 +597,131 @@ class StructReader:
         child._dev = self._dev
         child._read(FIELD_U8, 0, what="StructReader.readStruct")
         return child
+
+
+class _ListReader:
+    """A list resolved by one n = 1 list_heads_batch call: len(), and element reads that are one
+    n = 1 read_elements_batch call each (the element numbering is start = [0, count])."""
+
+    def __init__(self, parent: StructReader, pointer_index: int, kind: int, what: str):
+        self.reader, self.kind = parent, kind
+        d_in, off, ln = parent._framed()
+        dev = parent.device
+        self.head = torch.zeros(LIST_HEAD_BYTES, dtype=torch.uint8, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        list_heads_batch(d_in, off, ln, kind, pointer_index, self.head, count, st, parent.path)
+        _raise(int(st.item()), what)
+        self.count = int(count.item())
+        self.host_head = self.head.cpu().numpy().view(LIST_HEAD_DTYPE).copy()
+
+    def len(self) -> int:
+        return self.count
+
+    def __len__(self) -> int:
+        return self.count
+
+    def _check(self, k: int) -> int:
+        k = int(k)
+        if not 0 <= k < self.count:
+            raise IndexError(f"element {k} of a list of {self.count}")  # IndexOutOfBounds
+        return k
+
+
+class _ElementReader(StructReader):
+    """Element k of a list as a struct reader: StructListReader.get's result, or a pointer-list
+    slot as a struct of one pointer. Reads are n = 1 read_elements_batch calls over the one element."""
+
+    def __init__(self, lst: _ListReader, k: int, path=()):
+        super().__init__(lst.reader.message, path, lst.reader.device)
+        self._dev = lst.reader._framed()
+        self.list, self.k = lst, k
+
+    def _read(self, kind, offset, bit=0, what="StructReader"):
+        d_in, off, ln = self._dev
+        lst = self.list
+        # element k alone: a table of one element whose head starts at element k
+        h = lst.host_head.copy()
+        h["elems_off"][0] += self.k * 8 * (int(h["data_words"][0]) + int(h["pointer_words"][0]))
+        h["count"][0] = 1
+        head = torch.from_numpy(h.view(np.uint8)).to(self.device)
+        start = torch.tensor([0, 1], dtype=torch.int64, device=self.device)
+        out = torch.zeros(3, dtype=torch.int64, device=self.device)
+        st = torch.full((1,), -1, dtype=torch.int32, device=self.device)
+        read_elements_batch(d_in, off, ln, head, start, lst.kind, 1, [Field(kind, offset, bit, self.path)],
+                            out[0:1], out[1:2], st, out[2:3])
+        _raise(int(st.item()), what)
+        v, l, c = (int(x) for x in out.cpu().numpy().view(np.uint64))
+        return v, l, c
+
+    def read_struct(self, pointer_index: int) -> "StructReader":
+        child = _ElementReader(self.list, self.k, self.path + (pointer_index,))
+        child._read(FIELD_U8, 0, what="StructReader.readStruct")
+        return child
+
+    def _nested(self, pointer_index: int):
+        raise InvalidArgument("a list inside a list element is not reachable: list_heads_batch starts at the root")
+
+    read_struct_list = read_text_list = read_pointer_list = _nested
+
+
+class StructListReader(_ListReader):
+    """readStructList's result (message.zig:1165-1185, list_readers.zig:75-101)."""
+
+    def get(self, k: int) -> StructReader:
+        return _ElementReader(self, self._check(k))
+
+
+class TextListReader(_ListReader):
+    """readTextList's result (message.zig:1200-1210, list_readers.zig:103-144)."""
+
+    def get(self, k: int) -> bytes:
+        return _ElementReader(self, self._check(k)).read_text(0)
+
+
+class PointerListReader(_ListReader):
+    """readPointerList's result (message.zig:1212-1222, list_readers.zig:233-330)."""
+
+    def _elem(self, k):
+        return _ElementReader(self, self._check(k))
+
+    def get_text(self, k: int) -> bytes:
+        return self._elem(k).read_text(0)
+
+    def get_data(self, k: int) -> bytes:
+        return self._elem(k).read_data(0)
+
+    def get_u16_list(self, k: int) -> list:
+        return self._elem(k).read_u16_list(0)
+
+    def get_u32_list(self, k: int) -> list:
+        return self._elem(k).read_u32_list(0)
+
+    def get_u64_list(self, k: int) -> list:
+        return self._elem(k).read_u64_list(0)
+
+    def get_struct(self, k: int) -> StructReader:
+        return self._elem(k).read_struct(0)
+
+
+def _read_struct_list(self, pointer_index: int) -> StructListReader:
+    """readStructList (message.zig:1165-1185): one n = 1 list_heads_batch call."""
+    return StructListReader(self, pointer_index, LIST_STRUCT, "StructReader.readStructList")
+
+
+def _read_text_list(self, pointer_index: int) -> TextListReader:
+    """readTextList (message.zig:1200-1210)."""
+    return TextListReader(self, pointer_index, LIST_POINTER, "StructReader.readTextList")
+
+
+def _read_pointer_list(self, pointer_index: int) -> PointerListReader:
+    """readPointerList (message.zig:1212-1222)."""
+    return PointerListReader(self, pointer_index, LIST_POINTER, "StructReader.readPointerList")
+
+
+StructReader.read_struct_list = _read_struct_list
+StructReader.read_text_list = _read_text_list
+StructReader.read_pointer_list = _read_pointer_list
 
 
 class Reader:
@@ -1483,6 +1613,94 @@ def gather_batch(d_in, src_off, src_len, d_out, dst_off, status, cap=None, strea
     cap = d_out.numel() * d_out.element_size() if cap is None else int(cap)
     _raise(lib().capnp_packed_gather_batch(_ptr(d_in), _ptr(src_off), _ptr(src_len), n, _ptr(d_out), _ptr(dst_off),
                                            cap, _ptr(status), _stream(stream)), "gather_batch")
+
+
+# capnp_packed_list_heads_batch / capnp_packed_read_elements_batch list kinds
+LIST_STRUCT, LIST_POINTER = 0, 1
+
+
+class CListHead(ctypes.Structure):
+    """struct capnp_packed_list_head"""
+    _fields_ = [("elems_off", ctypes.c_uint64), ("count", ctypes.c_uint32), ("segment", ctypes.c_uint32),
+                ("seg_begin", ctypes.c_uint32), ("seg_bytes", ctypes.c_uint32), ("data_words", ctypes.c_uint16),
+                ("pointer_words", ctypes.c_uint16), ("status", ctypes.c_int32)]
+
+
+LIST_HEAD_DTYPE = np.dtype([("elems_off", "<u8"), ("count", "<u4"), ("segment", "<u4"), ("seg_begin", "<u4"),
+                            ("seg_bytes", "<u4"), ("data_words", "<u2"), ("pointer_words", "<u2"),
+                            ("status", "<i4")])
+LIST_HEAD_BYTES = 32
+
+
+def list_heads_batch(d_in, in_off, in_len, list_kind, pointer_index, head, count, status, path=(),
+                     stream=None) -> None:
+    """readStructList (LIST_STRUCT) or readTextList / readPointerList (LIST_POINTER) of pointer
+    `pointer_index` of the struct at `path` from the root, one list per framed message: head
+    (uint8, 32 bytes a message: CListHead / LIST_HEAD_DTYPE), count (int64) and status (int32)."""
+    n = _units(in_off, in_len, count, status)
+    if head is not None and head.numel() * head.element_size() < n * LIST_HEAD_BYTES:
+        raise InvalidArgument(f"head holds {head.numel() * head.element_size()} bytes for {n} messages")
+    path = tuple(int(p) for p in path)
+    arr = (ctypes.c_uint32 * max(1, len(path)))(*path)
+    _raise(lib().capnp_packed_list_heads_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, ctypes.addressof(arr),
+                                               len(path), pointer_index, list_kind, _ptr(head), _ptr(count),
+                                               _ptr(status), _stream(stream)), "list_heads_batch")
+
+
+def read_elements_batch(d_in, in_off, in_len, head, elem_start, list_kind, elem_cap, fields, value, length, status,
+                        count=None, parent=None, index=None, stream=None) -> None:
+    """Fields of every element of the lists `head` describes, as columns over the elements:
+    entry f * elem_cap + e of value / length / count (int64) and status (int32) is field f of
+    element e; parent / index (int32, optional) are the element's message and its place in that
+    message's list. elem_start = lengths_to_offsets(counts)."""
+    n = _units(in_off, in_len)
+    nf = len(fields)
+    elem_cap = int(elem_cap)
+    if elem_start is not None and elem_start.numel() < n + 1:
+        raise InvalidArgument(f"elem_start has {elem_start.numel()} entries for {n} messages")
+    if head is not None and head.numel() * head.element_size() < n * LIST_HEAD_BYTES:
+        raise InvalidArgument(f"head holds {head.numel() * head.element_size()} bytes for {n} messages")
+    for t in (value, length, status, count):
+        if t is not None and t.numel() < elem_cap * nf:
+            raise InvalidArgument(f"field-major output has {t.numel()} entries for {nf} fields x {elem_cap} elements")
+    for t in (parent, index):
+        if t is not None and t.numel() < elem_cap:
+            raise InvalidArgument(f"per-element output has {t.numel()} entries for {elem_cap} elements")
+    arr = _cfields(fields)
+    _raise(lib().capnp_packed_read_elements_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, _ptr(head),
+                                                  _ptr(elem_start), list_kind, elem_cap, ctypes.addressof(arr), nf,
+                                                  _ptr(parent), _ptr(index), _ptr(value), _ptr(length), _ptr(count),
+                                                  _ptr(status), _stream(stream)), "read_elements_batch")
+
+
+def read_list_batch(d_in, in_off, in_len, list_kind, pointer_index, fields, path=(), max_elements=None,
+                    stream=None) -> tuple:
+    """The whole chain: list_heads_batch -> lengths_to_offsets -> read_elements_batch. Returns
+    (head_status, counts, start, total, parent, index, value, length, count, status); the four
+    field outputs are [len(fields), capacity]. max_elements None: the total is read back (one
+    sync) and the outputs are allocated exactly, total an int. A number: that capacity is
+    allocated, nothing syncs and total is a device tensor (start[n:]) for the caller to compare:
+    elements past the capacity were not read."""
+    n = _units(in_off, in_len)
+    dev = in_off.device
+    head = torch.empty(n * LIST_HEAD_BYTES, dtype=torch.uint8, device=dev)
+    counts = torch.empty(n, dtype=torch.int64, device=dev)
+    head_status = torch.empty(n, dtype=torch.int32, device=dev)
+    list_heads_batch(d_in, in_off, in_len, list_kind, pointer_index, head, counts, head_status, path, stream)
+    start = lengths_to_offsets(counts, stream=stream)
+    if max_elements is None:
+        total = cap = int(start[n].item())
+    else:
+        cap = int(max_elements)
+        total = start[n:]
+    nf = len(fields)
+    out = torch.zeros((3, nf, cap), dtype=torch.int64, device=dev)
+    status = torch.zeros((nf, cap), dtype=torch.int32, device=dev)
+    parent = torch.zeros(cap, dtype=torch.int32, device=dev)
+    index = torch.zeros(cap, dtype=torch.int32, device=dev)
+    read_elements_batch(d_in, in_off, in_len, head, start, list_kind, cap, fields, out[0], out[1], status,
+                        out[2], parent, index, stream)
+    return head_status, counts, start, total, parent, index, out[0], out[1], out[2], status
 
 
 def lengths_to_offsets(lengths, base: int = 0, out=None, stream=None):

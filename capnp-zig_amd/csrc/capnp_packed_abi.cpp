@@ -905,6 +905,61 @@ int capnp_packed_gather_batch(const uint8_t* d_in, const uint64_t* d_src_off, co
                     "gather launch");
 }
 
+int capnp_packed_list_heads_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
+                                  const uint32_t* path, uint32_t path_len, uint32_t pointer_index,
+                                  uint32_t list_kind, capnp_packed_list_head* d_head, uint64_t* d_count,
+                                  int32_t* d_status, void* stream) {
+    if (list_kind > CAPNP_PACKED_LIST_POINTER) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown list kind");
+    if (path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
+    if (n == 0) return CAPNP_PACKED_OK;
+    if (!d_in || !d_in_off || !d_in_len || !d_head || !d_count || !d_status || (path_len && !path))
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_list_heads(d_in, d_in_off, d_in_len, n, path, path_len, pointer_index, list_kind,
+                                           d_head, d_count, d_status, static_cast<hipStream_t>(stream)),
+                    "list-heads launch");
+}
+
+int capnp_packed_read_elements_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                     uint32_t n, const capnp_packed_list_head* d_head, const uint64_t* d_elem_start,
+                                     uint32_t list_kind, uint64_t elem_cap, const capnp_packed_field* fields,
+                                     uint32_t n_fields, uint32_t* d_parent, uint32_t* d_index, uint64_t* d_value,
+                                     uint64_t* d_len, uint64_t* d_count, int32_t* d_status, void* stream) {
+    if (list_kind > CAPNP_PACKED_LIST_POINTER) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown list kind");
+    if (elem_cap >= (1ull << 32)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "elem_cap of 2^32 or more");
+    if (n_fields > CAPNP_PACKED_MAX_FIELDS) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "more than 32 fields");
+    if (n == 0 || elem_cap == 0) return CAPNP_PACKED_OK;
+    if (n_fields == 0) {  // the element numbering only
+        if (!d_parent && !d_index) return CAPNP_PACKED_OK;
+        if (!d_elem_start) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    } else {
+        if (!fields || !d_in || !d_in_off || !d_in_len || !d_head || !d_elem_start || !d_value || !d_len || !d_status)
+            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+        for (uint32_t f = 0; f < n_fields; ++f) {
+            const capnp_packed_field& a = fields[f];
+            if (a.kind > CAPNP_PACKED_FIELD_LIST_64) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown field kind");
+            if (a.bit > (a.kind == CAPNP_PACKED_FIELD_BOOL ? 7u : 0u))
+                return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bit is 0-7 for BOOL and 0 otherwise");
+            if (a.path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
+            if (list_kind == CAPNP_PACKED_LIST_POINTER) {  // the element is one pointer
+                if (a.path_len == 0 && a.kind <= CAPNP_PACKED_FIELD_BOOL)
+                    return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a pointer-list element has no data section");
+                if (a.path_len == 0 && a.offset != 0)
+                    return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a pointer-list element has pointer 0 only");
+                if (a.path_len && a.path[0] != 0)
+                    return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a pointer-list element has pointer 0 only");
+            }
+        }
+    }
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_read_elements(d_in, d_in_off, n, d_head, d_elem_start, list_kind, elem_cap, fields,
+                                              n_fields, d_parent, d_index, d_value, d_len, d_count, d_status,
+                                              static_cast<hipStream_t>(stream)),
+                    "read-elements launch");
+}
+
 size_t capnp_packed_scan_scratch_bytes(uint32_t n) { return cpk::scan_scratch_bytes(n); }
 
 int capnp_packed_lengths_to_offsets(const uint64_t* d_len, uint32_t n, uint64_t base, uint64_t* d_off,

@@ -136,6 +136,19 @@ hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint6
                          uint8_t* out, const uint64_t* dst_off, uint64_t out_cap, int32_t* status,
                          hipStream_t stream);
 
+// Struct lists and pointer lists as element tables (capnp_packed_list_heads_batch and
+// capnp_packed_read_elements_batch): `path` (at most CAPNP_PACKED_MAX_PATH) and
+// `fields` are host memory, checked by the caller, and go to the kernels by value; the grid of
+// launch_read_elements is sized from elem_cap (below 2^32, above 0).
+hipError_t launch_list_heads(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                             const uint32_t* path, uint32_t path_len, uint32_t pointer_index, uint32_t list_kind,
+                             capnp_packed_list_head* head, uint64_t* count, int32_t* status, hipStream_t stream);
+hipError_t launch_read_elements(const uint8_t* in, const uint64_t* in_off, uint32_t n,
+                                const capnp_packed_list_head* head, const uint64_t* elem_start, uint32_t list_kind,
+                                uint64_t elem_cap, const capnp_packed_field* fields, uint32_t n_fields,
+                                uint32_t* parent, uint32_t* index, uint64_t* value, uint64_t* len, uint64_t* count,
+                                int32_t* status, hipStream_t stream);
+
 hipError_t launch_generate(uint8_t* out, uint64_t n_units, uint64_t unit_bytes, uint64_t unit_base,
                            uint64_t seed, uint32_t thr, hipStream_t stream);
 

@@ -5606,6 +5606,7 @@ __global__ __launch_bounds__(kWvBlock) void split_walk_kernel(
 // host only: the per-stream side-launch context and the launch policy flags
 #include "kernels/side_launch.h"
 #include "kernels/struct_read.h"
+#include "kernels/list_read.h"
 
 namespace cpk {
 
@@ -6264,6 +6265,41 @@ hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint6
                          hipStream_t stream) {
     gather_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, src_off, src_len, n, out, dst_off, out_cap,
                                                                     status);
+    return hipGetLastError();
+}
+
+// `same` of a descriptor table: bit f set when field f's path is field f - 1's
+static SrFields sr_fields(const capnp_packed_field* fields, uint32_t n_fields) {
+    SrFields fs{};
+    for (uint32_t f = 0; f < n_fields; ++f) {
+        fs.f[f] = fields[f];
+        const capnp_packed_field& a = fields[f];
+        bool same = f > 0 && a.path_len == fields[f - 1].path_len;
+        for (uint32_t k = 0; same && k < a.path_len; ++k) same = a.path[k] == fields[f - 1].path[k];
+        if (same) fs.same |= 1u << f;
+    }
+    return fs;
+}
+
+hipError_t launch_list_heads(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                             const uint32_t* path, uint32_t path_len, uint32_t pointer_index, uint32_t list_kind,
+                             capnp_packed_list_head* head, uint64_t* count, int32_t* status, hipStream_t stream) {
+    LrPath p{};
+    for (uint32_t k = 0; k < path_len; ++k) p.p[k] = path[k];
+    list_heads_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, in_off, in_len, n, p, path_len,
+                                                                        pointer_index, list_kind, head, count, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_read_elements(const uint8_t* in, const uint64_t* in_off, uint32_t n,
+                                const capnp_packed_list_head* head, const uint64_t* elem_start, uint32_t list_kind,
+                                uint64_t elem_cap, const capnp_packed_field* fields, uint32_t n_fields,
+                                uint32_t* parent, uint32_t* index, uint64_t* value, uint64_t* len, uint64_t* count,
+                                int32_t* status, hipStream_t stream) {
+    const SrFields fs = sr_fields(fields, n_fields);
+    const uint32_t blocks = (uint32_t)((elem_cap + kBlock - 1) / kBlock);  // elem_cap < 2^32
+    read_elements_kernel<<<blocks, kBlock, 0, stream>>>(in, in_off, n, head, elem_start, list_kind, elem_cap, fs,
+                                                        n_fields, parent, index, value, len, count, status);
     return hipGetLastError();
 }
 

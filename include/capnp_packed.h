@@ -56,7 +56,10 @@ extern "C" {
  *     over framed messages: under DIALECT_CXX the bytes of capnp convert binary:packed).
  *   2, additions only: capnp_packed_read_fields_batch, capnp_packed_gather_batch, the
  *     capnp_packed_field descriptor and the CAPNP_PACKED_FIELD_* kinds (the root struct's and
- *     nested structs' scalar and slice reads as columns, and the slices as dense bytes). */
+ *     nested structs' scalar and slice reads as columns, and the slices as dense bytes).
+ *   2, additions only: capnp_packed_list_heads_batch, capnp_packed_read_elements_batch, the
+ *     capnp_packed_list_head record and the CAPNP_PACKED_LIST_* kinds (struct lists and pointer
+ *     lists as element tables). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -626,8 +629,8 @@ int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
  * Host-side checks, INVALID_ARGUMENT before any device work: n_fields > CAPNP_PACKED_MAX_FIELDS;
  * with n > 0 and n_fields > 0, a NULL array (d_count excepted), an unknown kind, bit > 7 or
  * bit != 0 on a kind other than BOOL, path_len > CAPNP_PACKED_MAX_PATH. n == 0 or n_fields == 0
- * is OK with no device work. Out of scope: struct and pointer lists, capabilities, XOR defaults,
- * the *Strict reads, UTF-8 validation.
+ * is OK with no device work. Out of scope: capabilities, XOR defaults, the *Strict reads, UTF-8
+ * validation; struct and pointer lists are capnp_packed_list_heads_batch's, below.
  * ------------------------------------------------------------------------ */
 #define CAPNP_PACKED_FIELD_U8 0u       /* readU8 (message.zig:1120) */
 #define CAPNP_PACKED_FIELD_U16 1u      /* readU16 (:1097), readUnionDiscriminant */
@@ -673,6 +676,113 @@ int capnp_packed_read_fields_batch(const uint8_t* d_in, const uint64_t* d_in_off
 int capnp_packed_gather_batch(const uint8_t* d_in, const uint64_t* d_src_off, const uint64_t* d_src_len,
                               uint32_t n, uint8_t* d_out, const uint64_t* d_dst_off, uint64_t out_cap,
                               int32_t* d_status, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Struct lists and pointer lists of decoded messages as element tables: the
+ * "explode" of a columnar reader. Message i contributes count[i] elements, and a field of all
+ * elements of all messages is one column of length sum(count). Three calls make the chain:
+ *   capnp_packed_list_heads_batch      one list per message: where its elements lie, how many
+ *   capnp_packed_lengths_to_offsets    d_count -> d_elem_start (n + 1 entries, base 0)
+ *   capnp_packed_read_elements_batch   fields of every element, as columns over the elements
+ * Both calls are asynchronous on `stream`, allocate nothing, keep no library state and are
+ * capturable in a hipGraph; `path` and `fields` are HOST memory, passed to the kernels by value.
+ *
+ * capnp_packed_list_heads_batch resolves, per message, the list at pointer `pointer_index` of
+ * the struct root.readStruct(path[0])...readStruct(path[path_len - 1]):
+ *   CAPNP_PACKED_LIST_STRUCT   readStructList (message.zig:1165-1185), i.e.
+ *                              resolveInlineCompositeList (:563-696)
+ *   CAPNP_PACKED_LIST_POINTER  readTextList / readPointerList (:1200-1222): element size 6
+ * d_count repeats head.count as a uint64 column of its own, so that it passes unchanged to
+ * capnp_packed_lengths_to_offsets; d_status repeats head.status. A failed head is all zero but
+ * for its status. Per message, in the reference's order (the first error is the status):
+ *   the message-level checks of capnp_packed_read_fields_batch: a misaligned offset or a length
+ *     of 4 GiB or more is INVALID_ARGUMENT; Message.init's table parse; getRootStruct; readStruct
+ *     along `path`;
+ *   the pointer slot: OUT_OF_BOUNDS (index past the pointer section), INVALID_POINTER (a null
+ *     word: the reference returns an error for a null list pointer, not an empty list);
+ *   LIST_STRUCT, resolveInlineCompositeList line by line (it does not go through resolvePointer:
+ *   there is no depth-8 chain, and a far pointer that lands on a far pointer is an error):
+ *     near list pointer: element size != 7 INVALID_INLINE_COMPOSITE_POINTER; a negative tag
+ *       position OUT_OF_BOUNDS; the tag word past its segment OUT_OF_BOUNDS (readWord); tag type
+ *       != 0, a negative count, or count * (data words + pointer words) > the pointer's word
+ *       count INVALID_INLINE_COMPOSITE_POINTER; the pointer's word count * 8 past the segment
+ *       OUT_OF_BOUNDS;
+ *     single far: INVALID_SEGMENT_ID, OUT_OF_BOUNDS (the landing pad); a landing word that is not
+ *       a list pointer INVALID_POINTER; then the near arm at the pad;
+ *     double far: INVALID_SEGMENT_ID, OUT_OF_BOUNDS (the 16-byte pad); a first word that is not a
+ *       single far pointer INVALID_FAR_POINTER; its segment INVALID_SEGMENT_ID; then by the second
+ *       word: a struct-typed word is the tag (layout A: bounds on exactly count * words,
+ *       OUT_OF_BOUNDS; :645's overflow guard, also OUT_OF_BOUNDS, cannot trip with 64-bit sizes);
+ *       a list pointer (layout B: element size != 7 INVALID_INLINE_COMPOSITE_POINTER, the tag at
+ *       the target checked as in the near arm); type 2 or 3 INVALID_INLINE_COMPOSITE_POINTER;
+ *     pointer type 0 or 3: INVALID_POINTER;
+ *   LIST_POINTER, resolveListPointerAt + resolveListPointer (:1187-1198, :525-561) exactly as the
+ *     slice kinds of capnp_packed_read_fields_batch (resolvePointer's errors with depth 8, the
+ *     bounds check on the list before the element size), then element size != 6 INVALID_POINTER.
+ * Host-side checks, INVALID_ARGUMENT before any device work: an unknown list_kind; path_len >
+ * CAPNP_PACKED_MAX_PATH; with n > 0 a NULL array (`path` may be NULL when path_len == 0).
+ * n == 0 is OK with NULL arrays.
+ *
+ * capnp_packed_read_elements_batch. d_elem_start = lengths_to_offsets(d_count, base 0). Element
+ * e lies in [0, min(d_elem_start[n], elem_cap)); it belongs to the message i with
+ * d_elem_start[i] <= e < d_elem_start[i + 1] (empty lists own no element) and is element
+ * k = e - d_elem_start[i] of that list: d_parent[e] = i, d_index[e] = k (either may be NULL).
+ * Outputs are field-major over elem_cap: entry f * elem_cap + e is field f of element e. Entries
+ * with e at or past the total are never written. The total stays on the device and the grid is
+ * sized from elem_cap, so the call needs no sync. AN UNTRUSTED MESSAGE CAN CLAIM A VERY LARGE
+ * LIST (a struct list of zero-word elements passes every check with up to 2^29 - 1 elements):
+ * elem_cap is what bounds the work and the output.
+ * If k >= d_head[i].count, the start array does not belong to these heads: every field of that
+ * element is INVALID_ARGUMENT and nothing of the message is read.
+ * The element is a struct reader:
+ *   LIST_STRUCT: StructListReader.get (list_readers.zig:87-100): the struct at elems_off +
+ *     k * 8 * (data_words + pointer_words) with the head's section sizes. get's own bounds check
+ *     cannot fail after an OK head (the head's call checked the whole list against its segment),
+ *     as EMPTY_MESSAGE cannot come out of a table parse.
+ *   LIST_POINTER: the pointer slot elems_off + 8 k as a struct of no data words and one pointer.
+ *     A descriptor with path_len 0, offset 0 and a slice kind is then check for check
+ *     TextListReader.get / PointerListReader.getText (:113-133, :258-272: null is empty text with
+ *     OK, element size != 2 INVALID_POINTER, one trailing NUL dropped), getData (:298-304) and
+ *     get{U16,U32,U64,F32,F64,Bool}List (:252-256, :308-324: null INVALID_POINTER, bounds before
+ *     the element size); one with path[0] == 0 is getStruct (:284-288) and then readStruct steps.
+ * From the element onward a field means what it means in capnp_packed_read_fields_batch: path
+ * steps, data reads with the schema-evolution default, slice reads, readText; `value` of a slice
+ * is the content's byte offset from d_in, so columns feed capnp_packed_gather_batch unchanged.
+ * The head's OK status stands for Message.init's checks, which are not redone: near pointers
+ * read no table, a far pointer reads the segment count and the other segment's bounds from the
+ * message's table. Reads: aligned 8-byte words of the message's table or of one of its segments,
+ * no byte outside [off, off + len) of the element's own message.
+ * Host-side checks, INVALID_ARGUMENT: those of capnp_packed_read_fields_batch on the descriptors;
+ * elem_cap >= 2^32; an unknown list_kind; under LIST_POINTER a data kind with path_len 0, offset
+ * != 0 with path_len 0, or path[0] != 0; with n > 0, elem_cap > 0 and n_fields > 0 a NULL array
+ * (d_parent, d_index and d_count excepted). n_fields == 0 is legal with d_parent or d_index
+ * non-NULL: the element numbering only. n == 0 or elem_cap == 0 is OK with no device work.
+ * IndexOutOfBounds (get past the count) has no status and needs none: no element lies past it.
+ * ------------------------------------------------------------------------ */
+#define CAPNP_PACKED_LIST_STRUCT 0u  /* readStructList (message.zig:1165-1185): resolveInlineCompositeList */
+#define CAPNP_PACKED_LIST_POINTER 1u /* readTextList / readPointerList (:1200-1222): element size 6 */
+typedef struct capnp_packed_list_head { /* 32 bytes, device memory, one per message */
+    uint64_t elems_off; /* byte offset FROM d_in of element 0 (struct list: first struct; pointer list: first pointer) */
+    uint32_t count;     /* elements; 0 when status != OK */
+    uint32_t segment;   /* the segment the elements lie in */
+    uint32_t seg_begin; /* that segment's byte offset in the message */
+    uint32_t seg_bytes; /* and its length */
+    uint16_t data_words, pointer_words; /* struct list: from the tag; pointer list: 0, 1 */
+    int32_t status;
+} capnp_packed_list_head;
+int capnp_packed_list_heads_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                  uint32_t n, const uint32_t* path /* HOST, path_len entries */,
+                                  uint32_t path_len, uint32_t pointer_index, uint32_t list_kind,
+                                  capnp_packed_list_head* d_head /* n */, uint64_t* d_count /* n */,
+                                  int32_t* d_status /* n */, void* stream);
+int capnp_packed_read_elements_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                     uint32_t n, const capnp_packed_list_head* d_head /* n */,
+                                     const uint64_t* d_elem_start /* n + 1 */, uint32_t list_kind,
+                                     uint64_t elem_cap, const capnp_packed_field* fields /* HOST */,
+                                     uint32_t n_fields, uint32_t* d_parent /* elem_cap; may be NULL */,
+                                     uint32_t* d_index /* elem_cap; may be NULL */, uint64_t* d_value,
+                                     uint64_t* d_len, uint64_t* d_count /* may be NULL */,
+                                     int32_t* d_status /* each n_fields * elem_cap */, void* stream);
 
 /* Exclusive scan of n lengths into n+1 offsets (d_off[0] = base, d_off[n] =
  * base + total), on device.

@@ -171,6 +171,36 @@ pub extern "capnp_packed" fn capnp_packed_gather_batch(
     d_in: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, n: u32,
     d_out: [*]u8, d_dst_off: [*]const u64, out_cap: u64, d_status: [*]i32, stream: ?*anyopaque,
 ) c_int;
+/// Struct lists and pointer lists as element tables (struct capnp_packed_list_head): where one
+/// message's list lies and how many elements it has.
+pub const list_struct: u32 = 0;
+pub const list_pointer: u32 = 1;
+pub const ListHead = extern struct {
+    elems_off: u64,
+    count: u32,
+    segment: u32,
+    seg_begin: u32,
+    seg_bytes: u32,
+    data_words: u16,
+    pointer_words: u16,
+    status: i32,
+};
+/// readStructList (list_struct) or readTextList / readPointerList (list_pointer) of pointer
+/// `pointer_index` of the struct at `path` (host memory) from the root, one list per message;
+/// d_count feeds capnp_packed_lengths_to_offsets unchanged.
+pub extern "capnp_packed" fn capnp_packed_list_heads_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    path: ?[*]const u32, path_len: u32, pointer_index: u32, list_kind: u32,
+    d_head: [*]ListHead, d_count: [*]u64, d_status: [*]i32, stream: ?*anyopaque,
+) c_int;
+/// Fields of every element of those lists as field-major columns over elem_cap; element e of
+/// [0, min(d_elem_start[n], elem_cap)) belongs to d_parent[e] and is its element d_index[e].
+pub extern "capnp_packed" fn capnp_packed_read_elements_batch(
+    d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u64, n: u32,
+    d_head: [*]const ListHead, d_elem_start: [*]const u64, list_kind: u32, elem_cap: u64,
+    fields: ?[*]const Field, n_fields: u32, d_parent: ?[*]u32, d_index: ?[*]u32,
+    d_value: ?[*]u64, d_len: ?[*]u64, d_count: ?[*]u64, d_status: ?[*]i32, stream: ?*anyopaque,
+) c_int;
 /// Class workspace for the *_batch_ws calls (graph-safe batches with no shared state): unit
 /// lists, the long-unit tile / window table and the decoder's piece records (~750 B per unit).
 /// d_ws must be 256-B aligned (hipMalloc's alignment); a misaligned one is InvalidArgument.
