@@ -1590,6 +1590,17 @@ def _cfields(fields):
     return arr
 
 
+def _check_field_major(columns, nf, rows, what):
+    for t in columns:
+        if t is not None and t.numel() < rows * nf:
+            raise InvalidArgument(f"field-major output has {t.numel()} entries for {nf} fields x {rows} {what}")
+
+
+def _check_head(head, n):
+    if head is not None and head.numel() * head.element_size() < n * LIST_HEAD_BYTES:
+        raise InvalidArgument(f"head holds {head.numel() * head.element_size()} bytes for {n} messages")
+
+
 def read_fields_batch(d_in, in_off, in_len, fields, value, length, status, count=None, stream=None) -> None:
     """getRootStruct + StructReader reads (message.zig:973-985, :1010-1443) of a batch of framed
     messages as columns: entry f * n + i of value / length / count (int64) and status (int32) is
@@ -1597,9 +1608,7 @@ def read_fields_batch(d_in, in_off, in_len, fields, value, length, status, count
     (value, length) columns feed gather_batch unchanged."""
     n = _units(in_off, in_len)
     nf = len(fields)
-    for t in (value, length, status, count):
-        if t is not None and t.numel() < n * nf:
-            raise InvalidArgument(f"field-major output has {t.numel()} entries for {nf} fields x {n} messages")
+    _check_field_major((value, length, status, count), nf, n, "messages")
     arr = _cfields(fields)  # read by the call itself (passed to the kernel by value): free after it
     _raise(lib().capnp_packed_read_fields_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n,
                                                 ctypes.addressof(arr), nf, _ptr(value), _ptr(length),
@@ -1638,8 +1647,7 @@ def list_heads_batch(d_in, in_off, in_len, list_kind, pointer_index, head, count
     `pointer_index` of the struct at `path` from the root, one list per framed message: head
     (uint8, 32 bytes a message: CListHead / LIST_HEAD_DTYPE), count (int64) and status (int32)."""
     n = _units(in_off, in_len, count, status)
-    if head is not None and head.numel() * head.element_size() < n * LIST_HEAD_BYTES:
-        raise InvalidArgument(f"head holds {head.numel() * head.element_size()} bytes for {n} messages")
+    _check_head(head, n)
     path = tuple(int(p) for p in path)
     arr = (ctypes.c_uint32 * max(1, len(path)))(*path)
     _raise(lib().capnp_packed_list_heads_batch(_ptr(d_in), _ptr(in_off), _ptr(in_len), n, ctypes.addressof(arr),
@@ -1658,11 +1666,8 @@ def read_elements_batch(d_in, in_off, in_len, head, elem_start, list_kind, elem_
     elem_cap = int(elem_cap)
     if elem_start is not None and elem_start.numel() < n + 1:
         raise InvalidArgument(f"elem_start has {elem_start.numel()} entries for {n} messages")
-    if head is not None and head.numel() * head.element_size() < n * LIST_HEAD_BYTES:
-        raise InvalidArgument(f"head holds {head.numel() * head.element_size()} bytes for {n} messages")
-    for t in (value, length, status, count):
-        if t is not None and t.numel() < elem_cap * nf:
-            raise InvalidArgument(f"field-major output has {t.numel()} entries for {nf} fields x {elem_cap} elements")
+    _check_head(head, n)
+    _check_field_major((value, length, status, count), nf, elem_cap, "elements")
     for t in (parent, index):
         if t is not None and t.numel() < elem_cap:
             raise InvalidArgument(f"per-element output has {t.numel()} entries for {elem_cap} elements")

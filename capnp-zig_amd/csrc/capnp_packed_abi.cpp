@@ -870,6 +870,15 @@ int capnp_packed_validate_batch(const uint8_t* d_in, const uint64_t* d_in_off, c
                     "validate launch");
 }
 
+// what every field descriptor must satisfy, for a root read and an element read alike
+static int check_field(const capnp_packed_field& a) {
+    if (a.kind > CAPNP_PACKED_FIELD_LIST_64) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown field kind");
+    if (a.bit > (a.kind == CAPNP_PACKED_FIELD_BOOL ? 7u : 0u))
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bit is 0-7 for BOOL and 0 otherwise");
+    if (a.path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
+    return CAPNP_PACKED_OK;
+}
+
 int capnp_packed_read_fields_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                    uint32_t n, const capnp_packed_field* fields, uint32_t n_fields,
                                    uint64_t* d_value, uint64_t* d_len, uint64_t* d_count, int32_t* d_status,
@@ -878,13 +887,8 @@ int capnp_packed_read_fields_batch(const uint8_t* d_in, const uint64_t* d_in_off
     if (n == 0 || n_fields == 0) return CAPNP_PACKED_OK;
     if (!fields || !d_in || !d_in_off || !d_in_len || !d_value || !d_len || !d_status)
         return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
-    for (uint32_t f = 0; f < n_fields; ++f) {
-        const capnp_packed_field& a = fields[f];
-        if (a.kind > CAPNP_PACKED_FIELD_LIST_64) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown field kind");
-        if (a.bit > (a.kind == CAPNP_PACKED_FIELD_BOOL ? 7u : 0u))
-            return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bit is 0-7 for BOOL and 0 otherwise");
-        if (a.path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
-    }
+    for (uint32_t f = 0; f < n_fields; ++f)
+        if (int st = check_field(fields[f])) return st;
     int st = ensure_device();
     if (st) return st;
     return launched(cpk::launch_read_fields(d_in, d_in_off, d_in_len, n, fields, n_fields, d_value, d_len, d_count,
@@ -938,10 +942,7 @@ int capnp_packed_read_elements_batch(const uint8_t* d_in, const uint64_t* d_in_o
             return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
         for (uint32_t f = 0; f < n_fields; ++f) {
             const capnp_packed_field& a = fields[f];
-            if (a.kind > CAPNP_PACKED_FIELD_LIST_64) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "unknown field kind");
-            if (a.bit > (a.kind == CAPNP_PACKED_FIELD_BOOL ? 7u : 0u))
-                return fail(CAPNP_PACKED_INVALID_ARGUMENT, "bit is 0-7 for BOOL and 0 otherwise");
-            if (a.path_len > CAPNP_PACKED_MAX_PATH) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "path longer than 4");
+            if (int st = check_field(a)) return st;
             if (list_kind == CAPNP_PACKED_LIST_POINTER) {  // the element is one pointer
                 if (a.path_len == 0 && a.kind <= CAPNP_PACKED_FIELD_BOOL)
                     return fail(CAPNP_PACKED_INVALID_ARGUMENT, "a pointer-list element has no data section");

@@ -3,35 +3,24 @@
 // scalar and slice reads of StructReader as columns, lane per message) and gather_kernel (the
 // slices as dense bytes, a ragged byte copy). DESIGN.md §2.13.
 // Leans on:
-//   common.h             kWave, kBlock, kMsgMaxSegs, the ST_* statuses, capnp_packed_field
-//   device_helpers.h     gload64, ptr_offset_words, wave_incl_sum, wave_lds_sync, store_partial16
+//   common.h             kWave, kBlock, the ST_* statuses
+//   device_helpers.h     lane_id, readlane, shfl_u64, wave_incl_sum, wave_lds_sync, store_partial16
+//   message_walk.h       mw_init, MwSegsLds, mw_root, mw_read_fields, MwStage, SrFields, kSrSegs, kSrGroup
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels/common.h"
 #include "kernels/device_helpers.h"
+#include "kernels/message_walk.h"
 
 namespace cpk {
 
 // ---------------------------------------------------------------------------
-// read_fields_kernel: message.zig:973-985 (getRootStruct), :451-561 (resolvePointer,
-// resolveStructPointer, resolveListPointer), :1051-1158 (data reads), :1187-1198, :1224-1235,
-// :1259-1443 (readStruct, the slice reads, readText), lane per message, every field of the
-// message in turn. The descriptors are kernel arguments (wave-uniform: scalar loads); `same`
-// has bit f set when field f's path is field f - 1's, so a struct is resolved once for a run
-// of fields that share it. Every load is an aligned 8-byte word of the message's segment table
-// or of one of its segments.
+// read_fields_kernel: Message.init, getRootStruct (message.zig:973-985), then every field of the
+// descriptor table in turn from the root struct, lane per message; the results go out through
+// LDS a group of fields at a time (message_walk.h has each of these and says why).
 // ---------------------------------------------------------------------------
-constexpr uint32_t kSrSegs = 4;         // segments whose bounds a lane keeps in LDS
-constexpr uint32_t kSrGroup = 4;        // fields whose results go out together
-constexpr uint32_t kSrFarDepth = 8;     // resolvePointer's depth (message.zig:493/526)
-
-struct SrFields {
-    capnp_packed_field f[CAPNP_PACKED_MAX_FIELDS];
-    uint32_t same;
-};
-
 __global__ __launch_bounds__(kBlock) void read_fields_kernel(const uint8_t* __restrict__ in,
                                                              const uint64_t* __restrict__ in_off,
                                                              const uint64_t* __restrict__ in_len, uint32_t n,
@@ -47,221 +36,15 @@ __global__ __launch_bounds__(kBlock) void read_fields_kernel(const uint8_t* __re
     const uint64_t moff = in_off[msg];
     const uint64_t len = in_len[msg];
     const uint8_t* const d = in + moff;
+    const MwStage out{res_all + threadIdx.x, msg, n, value, flen, count, status};
+    auto fail_all = [&](int32_t st) { out.store_all(n_fields, st); };
 
-    // A field's results wait in LDS (4 dwords: the value, the length, and the count or, with the
-    // top bit set, the status: lengths are below 4 GiB, counts below 2^29) and go out a group of
-    // fields at a time, so no store stands between a group's dependent loads (on gfx9 a load's
-    // vmcnt wait also waits for the stores issued before it). Worth 4% on the measured shape.
-    uint32_t* const res = res_all + threadIdx.x;
-    auto store = [&](uint32_t f, int32_t st, uint64_t v, uint64_t l, uint64_t c) {
-        const uint64_t at = (uint64_t)f * n + msg;
-        value[at] = v;
-        flen[at] = l;
-        if (count) count[at] = c;
-        status[at] = st;
-    };
-    auto put = [&](uint32_t f, int32_t st, uint64_t v, uint64_t l, uint64_t c) {
-        uint32_t* const r = res + 4 * kBlock * (f % kSrGroup);
-        r[0] = (uint32_t)v;
-        r[kBlock] = (uint32_t)(v >> 32);
-        r[2 * kBlock] = (uint32_t)l;
-        r[3 * kBlock] = st == ST_OK ? (uint32_t)c : 0x80000000u | (uint32_t)st;
-    };
-    auto flush = [&](uint32_t f0, uint32_t f1) {  // fields [f0, f1) of one group
-        for (uint32_t f = f0; f < f1; ++f) {
-            const uint32_t* const r = res + 4 * kBlock * (f % kSrGroup);
-            const uint32_t cs = r[3 * kBlock];
-            const bool ok = !(cs >> 31);
-            store(f, ok ? ST_OK : (int32_t)(cs & 0x7FFFFFFFu), (uint64_t)r[0] | ((uint64_t)r[kBlock] << 32),
-                  r[2 * kBlock], ok ? cs : 0u);
-        }
-    };
-    auto fail_all = [&](int32_t st) {
-        for (uint32_t f = 0; f < n_fields; ++f) store(f, st, 0, 0, 0);
-    };
-
-    // ---- Message.init (:341-394), message_init_kernel's statuses ---------------------------
-    if ((moff & 7) || len >= (1ull << 32)) return fail_all(ST_ARG);
-    if (len < 4) return fail_all(ST_EOS);
-    const uint64_t w0 = len >= 8 ? gload64(d) : (uint64_t)*reinterpret_cast<const uint32_t*>(d);
-    const uint32_t m1 = (uint32_t)w0;
-    if (m1 == 0xFFFFFFFFu) return fail_all(ST_SEGCOUNT);
-    if ((uint64_t)m1 + 1 > kMsgMaxSegs) return fail_all(ST_SEGLIMIT);
-    const uint32_t nseg = m1 + 1;
-    const uint64_t header = 4ull * (1 + nseg + ((nseg & 1) ? 0 : 1));
-    if (header > len) return fail_all(ST_TRUNC);
-    // table entry e (entry 0 the count, entry s + 1 segment s's words), given the word last read
-    auto entry = [&](uint32_t e, uint64_t& w) {
-        if ((e & 1) == 0) w = gload64(d + 4ull * e);
-        return (e & 1) ? (uint32_t)(w >> 32) : (uint32_t)w;
-    };
-    auto entry_at = [&](uint32_t e) {  // the same by a load of its own
-        const uint64_t w = gload64(d + 4ull * (e & ~1u));
-        return (e & 1) ? (uint32_t)(w >> 32) : (uint32_t)w;
-    };
-    // segment s < kSrSegs is [segb[s], segb[s + 1]) of the message: a column per lane in LDS, as
-    // in validate_kernel (in registers the compiler turns the lookup into a table in scratch)
-    uint32_t* const segb = segb_all + threadIdx.x;
-    {
-        uint64_t w = w0, acc = header;
-        segb[0] = (uint32_t)header;
-        for (uint32_t s = 0; s < nseg; ++s) {
-            acc += 8ull * entry(s + 1, w);
-            if (acc > len) return fail_all(ST_TRUNC);  // :380
-            if (s < kSrSegs) segb[kBlock * (s + 1)] = (uint32_t)acc;
-        }
-    }
-    // segment s < nseg: its offset in the message and its length
-    auto seg_lookup = [&](uint32_t s, uint64_t& off, uint64_t& slen) {
-        if (s < kSrSegs) {
-            off = segb[kBlock * s];
-            slen = segb[kBlock * (s + 1)] - off;
-            return;
-        }
-        uint64_t acc = segb[kBlock * kSrSegs];
-        for (uint32_t i = kSrSegs; i < s; ++i) acc += 8ull * entry_at(i + 1);
-        off = acc;
-        slen = 8ull * entry_at(s + 1);
-    };
-
-    // ---- resolvePointer (:451-490) ---------------------------------------------------------
-    struct Resolved {
-        uint32_t seg;
-        uint64_t pos, word, over;
-        bool has_over;
-    };
-    auto resolve = [&](Resolved& r) -> int32_t {
-        r.has_over = false;
-        r.over = 0;
-        for (uint32_t depth = kSrFarDepth;; --depth) {
-            if (depth == 0) return ST_NEST;  // PointerDepthLimit
-            if ((r.word & 3) != 2) return ST_OK;
-            const bool dbl = (r.word >> 2) & 1;
-            const uint64_t lpos = ((r.word >> 3) & 0x1FFFFFFFull) * 8;
-            const uint32_t fseg = (uint32_t)(r.word >> 32);
-            if (fseg >= nseg) return ST_SEGID;  // :431
-            uint64_t so, sl;
-            seg_lookup(fseg, so, sl);
-            if (lpos + (dbl ? 16 : 8) > sl) return ST_OOB;  // :435
-            const uint64_t landing = gload64(d + so + lpos);
-            if (!dbl) {
-                r.seg = fseg;
-                r.pos = lpos;
-                r.word = landing;
-                continue;
-            }
-            const uint64_t tag = gload64(d + so + lpos + 8);
-            if ((landing & 3) != 2 || ((landing >> 2) & 1)) return ST_FAR;  // :478/:480
-            if ((uint32_t)(landing >> 32) >= nseg) return ST_SEGID;       // :481
-            r.seg = (uint32_t)(landing >> 32);
-            r.pos = 0;
-            r.word = tag;
-            r.has_over = true;
-            r.over = ((landing >> 3) & 0x1FFFFFFFull) * 8;
-            return ST_OK;
-        }
-    };
-
-    // ---- resolveStructPointer (:492-523) ----------------------------------------------------
-    struct Struct {
-        uint32_t seg;
-        uint64_t soff;  // the segment's offset in the message
-        uint64_t off;   // the struct's offset in its segment
-        uint32_t dw, pc;
-    };
-    auto resolve_struct = [&](uint32_t seg, uint64_t pos, uint64_t word, Struct& s) -> int32_t {
-        Resolved r{seg, pos, word, 0, false};
-        if (int32_t st = resolve(r)) return st;
-        if (r.word == 0 || (r.word & 3) != 0) return ST_PTR;  // InvalidRootPointer
-        int64_t o = (int64_t)r.pos + 8 + ptr_offset_words(r.word) * 8;
-        if (r.has_over) o = (int64_t)r.over;
-        if (o < 0) return ST_PTR;
-        const uint32_t dw = (uint32_t)(r.word >> 32) & 0xFFFFu, pc = (uint32_t)(r.word >> 48);
-        uint64_t so, sl;
-        seg_lookup(r.seg, so, sl);
-        if ((uint64_t)o + 8ull * (dw + pc) > sl) return ST_TRUNC;  // :514
-        s = Struct{r.seg, so, (uint64_t)o, dw, pc};
-        return ST_OK;
-    };
-
-    // ---- getRootStruct (:973-985) ------------------------------------------------------------
-    Struct root{};
-    {
-        uint64_t so, sl;
-        seg_lookup(0, so, sl);
-        if (sl < 8) return fail_all(ST_TRUNC);
-        if (int32_t st = resolve_struct(0, 0, gload64(d + so), root)) return fail_all(st);
-    }
-
-    Struct cur = root;
-    int32_t cur_st = ST_OK;
-    for (uint32_t f = 0; f < n_fields; ++f) {
-        if (f && f % kSrGroup == 0) flush(f - kSrGroup, f);
-        const capnp_packed_field& F = fs.f[f];
-        if (!((fs.same >> f) & 1)) {  // readStruct along the path (:1224-1235)
-            cur = root;
-            cur_st = ST_OK;
-            for (uint32_t k = 0; k < F.path_len && cur_st == ST_OK; ++k) {
-                const uint32_t pi = F.path[k];
-                if (pi >= cur.pc) { cur_st = ST_OOB; break; }
-                const uint64_t ppos = cur.off + 8ull * cur.dw + 8ull * pi;
-                const uint64_t word = gload64(d + cur.soff + ppos);
-                if (word == 0) { cur_st = ST_PTR; break; }
-                Struct next{};
-                cur_st = resolve_struct(cur.seg, ppos, word, next);
-                if (cur_st == ST_OK) cur = next;
-            }
-        }
-        if (cur_st != ST_OK) { put(f, cur_st, 0, 0, 0); continue; }
-
-        if (F.kind <= CAPNP_PACKED_FIELD_BOOL) {  // the data section reads (:1051-1158)
-            const uint32_t width = F.kind == CAPNP_PACKED_FIELD_U64 ? 8u : F.kind == CAPNP_PACKED_FIELD_U32 ? 4u
-                                 : F.kind == CAPNP_PACKED_FIELD_U16 ? 2u : 1u;
-            if ((uint64_t)F.offset + width > 8ull * cur.dw) { put(f, ST_OK, 0, 0, 0); continue; }
-            const uint8_t* const p = d + cur.soff + cur.off + (F.offset & ~7u);
-            const uint32_t sh = (F.offset & 7u) * 8u;
-            uint64_t v = gload64(p) >> sh;
-            if ((F.offset & 7u) + width > 8u) v |= gload64(p + 8) << (64u - sh);  // sh > 0 here
-            if (width < 8) v &= (1ull << (8 * width)) - 1;
-            if (F.kind == CAPNP_PACKED_FIELD_BOOL) v = (v >> F.bit) & 1;
-            put(f, ST_OK, v, width, 1);
-            continue;
-        }
-
-        // the slice reads: resolveListPointerAt (:1187-1198), readText's front (:1417-1429)
-        const bool text = F.kind == CAPNP_PACKED_FIELD_TEXT;
-        if (F.offset >= cur.pc) { put(f, text ? ST_OK : ST_OOB, 0, 0, 0); continue; }
-        const uint64_t ppos = cur.off + 8ull * cur.dw + 8ull * F.offset;
-        Resolved r{cur.seg, ppos, gload64(d + cur.soff + ppos), 0, false};
-        if (r.word == 0) { put(f, text ? ST_OK : ST_PTR, 0, 0, 0); continue; }
-        // resolveListPointer (:525-561)
-        if (int32_t st = resolve(r)) { put(f, st, 0, 0, 0); continue; }
-        if (r.word == 0 || (r.word & 3) != 1) { put(f, ST_PTR, 0, 0, 0); continue; }
-        const uint32_t es = (uint32_t)(r.word >> 32) & 7u;
-        const uint64_t cnt = r.word >> 35;
-        int64_t co = (int64_t)r.pos + 8 + ptr_offset_words(r.word) * 8;
-        if (r.has_over) co = (int64_t)r.over;
-        if (co < 0) { put(f, ST_OOB, 0, 0, 0); continue; }  // :447
-        const uint64_t bytes = es == 0 ? 0 : es == 1 ? (cnt + 7) / 8 : es == 2 ? cnt : es == 3 ? 2 * cnt
-                             : es == 4 ? 4 * cnt : es == 7 ? 8 * (cnt + 1) : 8 * cnt;
-        uint64_t so, sl;
-        seg_lookup(r.seg, so, sl);
-        if ((uint64_t)co + bytes > sl) { put(f, ST_OOB, 0, 0, 0); continue; }  // :553
-        const uint32_t want = (text || F.kind == CAPNP_PACKED_FIELD_DATA) ? 2u
-                            : F.kind == CAPNP_PACKED_FIELD_LIST_BIT ? 1u
-                            : F.kind - CAPNP_PACKED_FIELD_LIST_16 + 3u;
-        if (es != want) { put(f, ST_PTR, 0, 0, 0); continue; }  // :1261 ..., InvalidTextPointer :1432
-        uint64_t l = bytes, c = cnt;
-        if (text && cnt) {  // one trailing NUL is not part of the text (:1439)
-            const uint64_t last = (uint64_t)co + cnt - 1;
-            if (((gload64(d + so + (last & ~7ull)) >> (8 * (last & 7))) & 0xFF) == 0) {
-                --l;
-                --c;
-            }
-        }
-        put(f, ST_OK, moff + so + (uint64_t)co, l, c);
-    }
-    flush((n_fields - 1) / kSrGroup * kSrGroup, n_fields);
+    uint32_t nseg;
+    if (int32_t st = mw_init(d, moff, len, segb_all + threadIdx.x, nseg)) return fail_all(st);
+    MwSegsLds sg{d, nseg, segb_all + threadIdx.x};
+    MwStruct root{};
+    if (int32_t st = mw_root(sg, root)) return fail_all(st);
+    mw_read_fields(sg, moff, root, fs, n_fields, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -50,6 +50,11 @@
 //   kernels/read_message.h      packed_header, read_header_kernel
 //   kernels/generate_scan.h     generate_kernel and the offsets scan
 //   kernels/side_launch.h       host only: StreamCtx / SideLaunch, the launch flags
+//   kernels/message_walk.h      the walk of a decoded message (mw_*): Message.init's front,
+//                               getRootStruct, the pointer resolution, one field's read, the
+//                               LDS result staging
+//   kernels/struct_read.h       read_fields_kernel, gather_kernel
+//   kernels/list_read.h         list_heads_kernel, read_elements_kernel
 // The order contract. This file includes every header under kernels/ directly, exactly once
 // (tests/test_kernel_headers.py), each where its section was; a header's own includes only name
 // what it leans on and are no-ops by then. The sections still in this file and the includes
@@ -5605,6 +5610,8 @@ __global__ __launch_bounds__(kWvBlock) void split_walk_kernel(
 #include "kernels/generate_scan.h"
 // host only: the per-stream side-launch context and the launch policy flags
 #include "kernels/side_launch.h"
+// reads on decoded messages: the shared walk (device functions only), then the kernels
+#include "kernels/message_walk.h"
 #include "kernels/struct_read.h"
 #include "kernels/list_read.h"
 
@@ -6244,30 +6251,6 @@ hipError_t launch_scan(const uint64_t* len, uint32_t n, uint64_t base, uint64_t*
     return hipGetLastError();
 }
 
-hipError_t launch_read_fields(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
-                              const capnp_packed_field* fields, uint32_t n_fields, uint64_t* value, uint64_t* len,
-                              uint64_t* count, int32_t* status, hipStream_t stream) {
-    SrFields fs{};
-    for (uint32_t f = 0; f < n_fields; ++f) {
-        fs.f[f] = fields[f];
-        const capnp_packed_field& a = fields[f];
-        bool same = f > 0 && a.path_len == fields[f - 1].path_len;
-        for (uint32_t k = 0; same && k < a.path_len; ++k) same = a.path[k] == fields[f - 1].path[k];
-        if (same) fs.same |= 1u << f;
-    }
-    read_fields_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, in_off, in_len, n, fs, n_fields, value,
-                                                                         len, count, status);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint64_t* src_len, uint32_t n,
-                         uint8_t* out, const uint64_t* dst_off, uint64_t out_cap, int32_t* status,
-                         hipStream_t stream) {
-    gather_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, src_off, src_len, n, out, dst_off, out_cap,
-                                                                    status);
-    return hipGetLastError();
-}
-
 // `same` of a descriptor table: bit f set when field f's path is field f - 1's
 static SrFields sr_fields(const capnp_packed_field* fields, uint32_t n_fields) {
     SrFields fs{};
@@ -6279,6 +6262,23 @@ static SrFields sr_fields(const capnp_packed_field* fields, uint32_t n_fields) {
         if (same) fs.same |= 1u << f;
     }
     return fs;
+}
+
+hipError_t launch_read_fields(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
+                              const capnp_packed_field* fields, uint32_t n_fields, uint64_t* value, uint64_t* len,
+                              uint64_t* count, int32_t* status, hipStream_t stream) {
+    const SrFields fs = sr_fields(fields, n_fields);
+    read_fields_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, in_off, in_len, n, fs, n_fields, value,
+                                                                         len, count, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather(const uint8_t* in, const uint64_t* src_off, const uint64_t* src_len, uint32_t n,
+                         uint8_t* out, const uint64_t* dst_off, uint64_t out_cap, int32_t* status,
+                         hipStream_t stream) {
+    gather_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, src_off, src_len, n, out, dst_off, out_cap,
+                                                                    status);
+    return hipGetLastError();
 }
 
 hipError_t launch_list_heads(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
