@@ -218,6 +218,8 @@ SIGNATURES = {
                                                       _vp, _vp, _vp]),
     "capnp_packed_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64, _vp,
                                                  _vp]),
+    "capnp_packed_build_fields_batch": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint32, _vp, ctypes.c_uint32,
+                                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "capnp_packed_list_heads_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
                                                      ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "capnp_packed_read_elements_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
@@ -394,17 +396,70 @@ def frame_segments(segments) -> bytes:
 
 
 class MessageBuilder:
-    """Segment-level mirror of MessageBuilder (message.zig:1643). Only the
-    serialization surface is mirrored; struct/list building is out of scope."""
+    """Mirror of MessageBuilder (message.zig:1643): the serialization surface over segments the
+    caller gives, and single-segment struct building (allocate_struct), which records builder
+    calls and runs them as one n = 1 capnp_packed_build_fields_batch call on the device in
+    to_bytes(); there is no CPU path. The two do not mix: allocate_struct wants an empty message
+    and create_segment refuses once a root is recorded. Struct lists, pointer lists and other
+    segments are out of scope."""
 
-    def __init__(self):
+    def __init__(self, device="cuda"):
         self.segments: list[bytearray] = []
+        self.device = device
+        self._ops: list = []     # BuildOp, in call order
+        self._values: list = []  # per op: an int (data kinds), bytes (slices) or None (structs)
+        self._counts: list = []
 
     def create_segment(self, data=b"") -> int:
+        if self._ops:
+            raise InvalidArgument("a message built by allocate_struct has segment 0 only")
         self.segments.append(bytearray(data))
         return len(self.segments) - 1
 
+    def allocate_struct(self, data_words: int, pointer_words: int) -> "StructBuilder":
+        """allocateStruct (message.zig:2061-2101) of the root struct in segment 0."""
+        if self._ops or self.segments:
+            raise InvalidArgument("allocate_struct builds the root of an empty message")
+        return StructBuilder(self, self._record(BuildOp(BUILD_STRUCT, 0, data_words=data_words,
+                                                        pointer_words=pointer_words), None))
+
+    def _record(self, op, value, count=0) -> int:
+        self._ops.append(op)
+        self._values.append(value)
+        self._counts.append(count)
+        return len(self._ops) - 1
+
+    def _build(self) -> bytes:
+        nops = len(self._ops)
+        pool = bytearray()
+        cols = np.zeros((3, nops), dtype=np.uint64)
+        for k, v in enumerate(self._values):
+            if isinstance(v, (bytes, bytearray)):
+                cols[0, k], cols[1, k], cols[2, k] = len(pool), len(v), self._counts[k]
+                pool += v
+            elif v is not None:
+                cols[0, k] = v
+        dev = self.device
+        d_pool = torch.from_numpy(np.frombuffer(bytes(pool) + b"\0" * 16, dtype=np.uint8).copy()).to(dev)
+        d_cols = torch.from_numpy(cols.view(np.int64)).to(dev)
+        out_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        build_fields_batch(d_pool, self._ops, d_cols[0], d_cols[1], None, None, None, out_len, status, d_cols[2],
+                           pool_len=len(pool))
+        _raise(int(status.item()), "MessageBuilder.to_bytes")
+        size = int(out_len.item())
+        d_out = torch.empty(size, dtype=torch.uint8, device=dev)
+        off = torch.zeros(1, dtype=torch.int64, device=dev)
+        build_fields_batch(d_pool, self._ops, d_cols[0], d_cols[1], d_out, off, out_len.clone(), out_len, status,
+                           d_cols[2], pool_len=len(pool))
+        _raise(int(status.item()), "MessageBuilder.to_bytes")
+        return d_out.cpu().numpy().tobytes()
+
     def to_bytes(self) -> bytes:
+        if self._ops:
+            framed = self._build()
+            self.segments = [bytearray(framed[8:])]  # one segment: an 8-byte table
+            return framed
         if not self.segments:
             self.create_segment()
         return frame_segments(self.segments)
@@ -424,6 +479,58 @@ class MessageBuilder:
     def write_packed_to(self, writer, dialect="zig") -> None:
         """message.zig:2209-2213."""
         writer.write(self.to_packed_bytes(dialect))
+
+
+class StructBuilder:
+    """Mirror of StructBuilder (message/struct_builder.zig:332-989) for one struct of a
+    MessageBuilder's segment 0: every write records one op of the message's build."""
+
+    def __init__(self, message: MessageBuilder, op_index: int):
+        self.message, self.op_index = message, op_index
+
+    def _data(self, kind, byte_offset, value, bit=0):
+        self.message._record(BuildOp(kind, byte_offset, bit, self.op_index), int(value))
+
+    def _slice(self, kind, pointer_index, data, count=0):
+        self.message._record(BuildOp(kind, pointer_index, 0, self.op_index), bytes(data), count)
+
+    def write_u8(self, byte_offset: int, value: int) -> None:
+        self._data(FIELD_U8, byte_offset, value & 0xFF)
+
+    def write_u16(self, byte_offset: int, value: int) -> None:
+        self._data(FIELD_U16, byte_offset, value & 0xFFFF)
+
+    def write_u32(self, byte_offset: int, value: int) -> None:
+        self._data(FIELD_U32, byte_offset, value & 0xFFFFFFFF)
+
+    def write_u64(self, byte_offset: int, value: int) -> None:
+        self._data(FIELD_U64, byte_offset, value & 0xFFFFFFFFFFFFFFFF)
+
+    def write_bool(self, byte_offset: int, bit_offset: int, value: bool) -> None:
+        self._data(FIELD_BOOL, byte_offset, 1 if value else 0, bit_offset)
+
+    def write_text(self, pointer_index: int, text) -> None:
+        self._slice(FIELD_TEXT, pointer_index, text.encode() if isinstance(text, str) else text)
+
+    def write_data(self, pointer_index: int, data) -> None:
+        self._slice(FIELD_DATA, pointer_index, data)
+
+    def write_u16_list(self, pointer_index: int, values) -> None:
+        self._slice(FIELD_LIST_16, pointer_index, np.asarray(values, dtype="<u2").tobytes())
+
+    def write_u32_list(self, pointer_index: int, values) -> None:
+        self._slice(FIELD_LIST_32, pointer_index, np.asarray(values, dtype="<u4").tobytes())
+
+    def write_u64_list(self, pointer_index: int, values) -> None:
+        self._slice(FIELD_LIST_64, pointer_index, np.asarray(values, dtype="<u8").tobytes())
+
+    def write_bool_list(self, pointer_index: int, values) -> None:
+        bits = np.asarray(values, dtype=bool)
+        self._slice(FIELD_LIST_BIT, pointer_index, np.packbits(bits, bitorder="little").tobytes(), len(bits))
+
+    def init_struct(self, pointer_index: int, data_words: int, pointer_words: int) -> "StructBuilder":
+        return StructBuilder(self.message, self.message._record(
+            BuildOp(BUILD_STRUCT, pointer_index, 0, self.op_index, data_words, pointer_words), None))
 
 
 class Message:
@@ -1622,6 +1729,62 @@ def gather_batch(d_in, src_off, src_len, d_out, dst_off, status, cap=None, strea
     cap = d_out.numel() * d_out.element_size() if cap is None else int(cap)
     _raise(lib().capnp_packed_gather_batch(_ptr(d_in), _ptr(src_off), _ptr(src_len), n, _ptr(d_out), _ptr(dst_off),
                                            cap, _ptr(status), _stream(stream)), "gather_batch")
+
+
+# capnp_packed_build_fields_batch (include/capnp_packed.h)
+BUILD_STRUCT = 16
+BUILD_ABSENT = 0xFFFFFFFFFFFFFFFF
+MAX_BUILD_OPS = 32
+MAX_BUILD_WORDS = 64
+
+
+class CBuildOp(ctypes.Structure):
+    """struct capnp_packed_build_op"""
+    _fields_ = [("kind", ctypes.c_uint32), ("target", ctypes.c_uint32), ("offset", ctypes.c_uint32),
+                ("bit", ctypes.c_uint32), ("data_words", ctypes.c_uint16), ("pointer_words", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+class BuildOp:
+    """One builder call of build_fields_batch: a FIELD_* kind as a write, or BUILD_STRUCT
+    (op 0: allocateStruct, later: initStruct). target is the BUILD_STRUCT op written into;
+    offset is a byte offset in its data section (data kinds) or a pointer index."""
+
+    def __init__(self, kind: int, offset: int, bit: int = 0, target: int = 0, data_words: int = 0,
+                 pointer_words: int = 0):
+        self.kind, self.offset, self.bit, self.target = int(kind), int(offset), int(bit), int(target)
+        self.data_words, self.pointer_words = int(data_words), int(pointer_words)
+
+    def __repr__(self):
+        return (f"BuildOp(kind={self.kind}, offset={self.offset}, bit={self.bit}, target={self.target}, "
+                f"data_words={self.data_words}, pointer_words={self.pointer_words})")
+
+    def c(self) -> CBuildOp:
+        return CBuildOp(self.kind, self.target, self.offset, self.bit, self.data_words, self.pointer_words,
+                        (ctypes.c_uint32 * 3)(0, 0, 0))
+
+
+def build_fields_batch(d_pool, ops, value, length, d_out, out_off, out_cap, out_len, status, count=None,
+                       pool_len=None, stream=None) -> None:
+    """MessageBuilder.allocateStruct, the StructBuilder writes and toBytes (message.zig:1643-2170,
+    message/struct_builder.zig:332-989) over a batch: the ops are applied to every message, with
+    values from the op-major columns (entry k * n + i of value / length / count, int64, is op k of
+    message i; a slice is d_pool[value : value + length]). Message i is written at
+    d_out[out_off[i]:] and out_len[i] is its framed length; d_out=None gives sizes only."""
+    n = _units(out_len, status)
+    nops = len(ops)
+    _check_field_major((value, length, count), nops, n, "messages")
+    if d_out is not None:
+        _units(out_len, out_off, out_cap)  # out_off may be a lengths_to_offsets result (n + 1 entries)
+    if pool_len is None:
+        pool_len = 0 if d_pool is None else d_pool.numel() * d_pool.element_size()
+    arr = (CBuildOp * max(1, nops))()  # read by the call itself (passed to the kernel by value)
+    for i, o in enumerate(ops):
+        arr[i] = o.c()
+    _raise(lib().capnp_packed_build_fields_batch(_ptr(d_pool), int(pool_len), n, ctypes.addressof(arr), nops,
+                                                 _ptr(value), _ptr(length), _ptr(count), _ptr(d_out),
+                                                 _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
+                                                 _stream(stream)), "build_fields_batch")
 
 
 # capnp_packed_list_heads_batch / capnp_packed_read_elements_batch list kinds

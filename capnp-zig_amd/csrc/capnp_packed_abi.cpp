@@ -961,6 +961,26 @@ int capnp_packed_read_elements_batch(const uint8_t* d_in, const uint64_t* d_in_o
                     "read-elements launch");
 }
 
+int capnp_packed_build_fields_batch(const uint8_t* d_pool, uint64_t pool_len, uint32_t n,
+                                    const capnp_packed_build_op* ops, uint32_t n_ops, const uint64_t* d_value,
+                                    const uint64_t* d_len, const uint64_t* d_count, uint8_t* d_out,
+                                    const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len,
+                                    int32_t* d_status, void* stream) {
+    if (n_ops > CAPNP_PACKED_MAX_BUILD_OPS) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "more than 32 build ops");
+    if (n == 0) return CAPNP_PACKED_OK;
+    cpk::SbPlan plan;
+    if (const char* why = cpk::sb_compile(ops, n_ops, &plan)) return fail(CAPNP_PACKED_INVALID_ARGUMENT, why);
+    if (!d_value || !d_len || !d_out_len || !d_status || (d_out && (!d_out_off || !d_out_cap)) ||
+        (pool_len && !d_pool))
+        return fail(CAPNP_PACKED_INVALID_ARGUMENT, "null batch pointer");
+    if (plan.has_bits && !d_count) return fail(CAPNP_PACKED_INVALID_ARGUMENT, "d_count is null with a LIST_BIT op");
+    int st = ensure_device();
+    if (st) return st;
+    return launched(cpk::launch_build_fields(d_pool, pool_len, n, plan, d_value, d_len, d_count, d_out, d_out_off,
+                                             d_out_cap, d_out_len, d_status, static_cast<hipStream_t>(stream)),
+                    "build-fields launch");
+}
+
 size_t capnp_packed_scan_scratch_bytes(uint32_t n) { return cpk::scan_scratch_bytes(n); }
 
 int capnp_packed_lengths_to_offsets(const uint64_t* d_len, uint32_t n, uint64_t base, uint64_t* d_off,

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "build_plan.h"
 #include "capnp_packed.h"
 
 namespace cpk {
@@ -148,6 +149,14 @@ hipError_t launch_read_elements(const uint8_t* in, const uint64_t* in_off, uint3
                                 uint64_t elem_cap, const capnp_packed_field* fields, uint32_t n_fields,
                                 uint32_t* parent, uint32_t* index, uint64_t* value, uint64_t* len, uint64_t* count,
                                 int32_t* status, hipStream_t stream);
+
+// MessageBuilder / StructBuilder over a batch (capnp_packed_build_fields_batch):
+// the plan (build_plan.h's sb_compile, which is the caller's check of the ops) goes to the kernel
+// by value; out == nullptr gives lengths and statuses only.
+hipError_t launch_build_fields(const uint8_t* pool, uint64_t pool_len, uint32_t n, const SbPlan& plan,
+                               const uint64_t* value, const uint64_t* len, const uint64_t* count, uint8_t* out,
+                               const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
+                               hipStream_t stream);
 
 hipError_t launch_generate(uint8_t* out, uint64_t n_units, uint64_t unit_bytes, uint64_t unit_base,
                            uint64_t seed, uint32_t thr, hipStream_t stream);

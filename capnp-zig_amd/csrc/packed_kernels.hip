@@ -55,6 +55,7 @@
 //                               LDS result staging
 //   kernels/struct_read.h       read_fields_kernel, gather_kernel
 //   kernels/list_read.h         list_heads_kernel, read_elements_kernel
+//   kernels/struct_build.h      build_fields_kernel (its plan and layout: build_plan.h, no HIP)
 // The order contract. This file includes every header under kernels/ directly, exactly once
 // (tests/test_kernel_headers.py), each where its section was; a header's own includes only name
 // what it leans on and are no-ops by then. The sections still in this file and the includes
@@ -5614,6 +5615,8 @@ __global__ __launch_bounds__(kWvBlock) void split_walk_kernel(
 #include "kernels/message_walk.h"
 #include "kernels/struct_read.h"
 #include "kernels/list_read.h"
+// the write side: messages built from columns
+#include "kernels/struct_build.h"
 
 namespace cpk {
 
@@ -6300,6 +6303,15 @@ hipError_t launch_read_elements(const uint8_t* in, const uint64_t* in_off, uint3
     const uint32_t blocks = (uint32_t)((elem_cap + kBlock - 1) / kBlock);  // elem_cap < 2^32
     read_elements_kernel<<<blocks, kBlock, 0, stream>>>(in, in_off, n, head, elem_start, list_kind, elem_cap, fs,
                                                         n_fields, parent, index, value, len, count, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_build_fields(const uint8_t* pool, uint64_t pool_len, uint32_t n, const SbPlan& plan,
+                               const uint64_t* value, const uint64_t* len, const uint64_t* count, uint8_t* out,
+                               const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
+                               hipStream_t stream) {
+    build_fields_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(pool, pool_len, n, plan, value, len, count,
+                                                                          out, out_off, out_cap, out_len, status);
     return hipGetLastError();
 }
 

@@ -59,7 +59,10 @@ extern "C" {
  *     nested structs' scalar and slice reads as columns, and the slices as dense bytes).
  *   2, additions only: capnp_packed_list_heads_batch, capnp_packed_read_elements_batch, the
  *     capnp_packed_list_head record and the CAPNP_PACKED_LIST_* kinds (struct lists and pointer
- *     lists as element tables). */
+ *     lists as element tables).
+ *   2, additions only: capnp_packed_build_fields_batch, the capnp_packed_build_op descriptor and
+ *     the CAPNP_PACKED_BUILD_* constants (single-segment struct building over a batch: columns to
+ *     framed messages). */
 #define CAPNP_PACKED_ABI_VERSION 2u
 
 /* Status codes. The first four mirror the reference's error set
@@ -783,6 +786,90 @@ int capnp_packed_read_elements_batch(const uint8_t* d_in, const uint64_t* d_in_o
                                      uint32_t* d_index /* elem_cap; may be NULL */, uint64_t* d_value,
                                      uint64_t* d_len, uint64_t* d_count /* may be NULL */,
                                      int32_t* d_status /* each n_fields * elem_cap */, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Struct building over a batch: the inverse of capnp_packed_read_fields_batch
+ * plus capnp_packed_gather_batch. One fixed sequence of builder calls (`ops`, HOST memory, passed
+ * to the kernel by value as a plan) is applied to n messages whose values come from device
+ * columns; message i leaves as the bytes of toBytes() at d_out + d_out_off[i]. The result feeds
+ * capnp_packed_encode_framed_batch / _dense_batch unchanged.
+ * Columns are op-major: entry k * n + i belongs to op k of message i.
+ *   data kinds (U8..U64, BOOL)  the value is d_value's low bits; d_count is ignored, and so is
+ *                               d_len unless it is CAPNP_PACKED_BUILD_ABSENT
+ *   slice kinds                 the content is d_pool[d_value .. + d_len): TEXT without its NUL
+ *                               (what the read returns), LIST_BIT with d_len the byte length and
+ *                               d_count the element count, LIST_16/32/64 with d_len in bytes
+ *   BUILD_STRUCT                ignores its column entries
+ * so the (value, len, count) columns capnp_packed_read_fields_batch wrote pass back unchanged.
+ * Per message the call runs this reference sequence, everything in segment 0, and takes
+ * toBytes() (message.zig:2123-2170):
+ *   MessageBuilder.init; allocateStruct(op0.data_words, op0.pointer_words) (:2061-2101);
+ *   then each further op in order, an op whose d_len entry is CAPNP_PACKED_BUILD_ABSENT being
+ *   skipped (BUILD_STRUCT ops always run), so that its pointer stays null / its bytes stay 0:
+ *     U8..U64   writeU8/16/32/64(offset, value), non-strict: a write that does not lie wholly
+ *               inside the target's data section is dropped (struct_builder.zig:356-430)
+ *     BOOL      writeBool(offset, bit, value & 1) (:449-458)
+ *     TEXT      writeText -> writeTextPointer (message.zig:1780-1815): len + 1 bytes with the NUL
+ *     DATA, LIST_16/32/64, LIST_BIT   writeData / writeU16List .. / writeBoolList and a set of
+ *               every element -> writeListPointer (:1909-1948): the pool bytes, padded to the word
+ *               with zeros; bits past `count` in a bit list's last byte are written as 0
+ *     BUILD_STRUCT  target.initStruct(offset, data_words, pointer_words) -> writeStructPointer
+ *               (:1834-1886); (0, 0) writes a null pointer and allocates nothing
+ * Every allocation is appended to segment 0 in op order. Later ops win where data writes overlap
+ * (unions); BOOL is a read-modify-write of one bit.
+ * Host-side checks, INVALID_ARGUMENT before any device work: n_ops > CAPNP_PACKED_MAX_BUILD_OPS;
+ * with n > 0: n_ops == 0 or op 0 not BUILD_STRUCT, an unknown kind, bit > 7 or bit != 0 off BOOL,
+ * non-zero reserved, target not an earlier BUILD_STRUCT op, a pointer index >= the target's
+ * pointer_words (the reference's PointerIndexOutOfBounds, static here), two ops on one pointer
+ * slot of one struct (the reference would orphan the first allocation), the words of every struct
+ * + 1 > CAPNP_PACKED_MAX_BUILD_WORDS, a NULL array (d_pool may be NULL with pool_len 0; d_out NULL
+ * asks for sizes only and then d_out_off / d_out_cap are not read), d_count NULL with a LIST_BIT
+ * op. n == 0 is OK with NULL arrays.
+ * Per message, the first that applies (a failed message writes no byte and gets d_out_len 0, but
+ * OUT_OF_SPACE reports the needed length):
+ *   1. d_out + d_out_off[i] is not a multiple of 8                          INVALID_ARGUMENT
+ *   2. per slice op in order, not absent, and per op in this order:
+ *        LIST_16/32/64 length not a multiple of the element width, or
+ *        LIST_BIT with d_len != (d_count + 7) / 8                           INVALID_ARGUMENT
+ *        an element count of 2^29 or more (TEXT: len + 1)                   LIST_TOO_LARGE
+ *        the slice not inside [0, pool_len), the sum taken without wrapping OUT_OF_BOUNDS
+ *   3. a framed length of 4 GiB or more                                     MESSAGE_TOO_LARGE
+ *   4. the framed length > d_out_cap[i]                                     OUT_OF_SPACE
+ * LIST_TOO_LARGE has no counterpart in the reference: its makeListPointer (message.zig:37-43)
+ * silently drops the bits of a count that does not fit the pointer's 29, so no defined answer
+ * exists for such a list. With d_out == NULL only d_out_len and d_status are produced and rules
+ * 1 and 4 do not apply.
+ * Contract: every byte of [d_out_off[i], + d_out_len[i]) of an OK message is written by the call
+ * (the output need not be zeroed) and no byte of d_out outside those ranges is modified. Loads
+ * from the pool are aligned 16-byte chunks that hold a byte of the slice (capnp_packed_gather_batch's
+ * rule); nothing is read from the pool for a failed message. Asynchronous on `stream`, no
+ * allocation, no workspace, no library state, no atomics, capturable in a hipGraph.
+ * Parallelism: as capnp_packed_gather_batch. Slices of at most 512 bytes are spread over a wave
+ * by 16-byte pieces; a longer slice is copied by ONE wave and is not tiled across waves.
+ * Out of scope: other segments and the *InSegment variants, struct lists and pointer lists,
+ * capabilities, the *Strict writes, rewriting a pointer.
+ * ------------------------------------------------------------------------ */
+#define CAPNP_PACKED_BUILD_STRUCT 16u        /* op 0: allocateStruct; later: StructBuilder.initStruct */
+#define CAPNP_PACKED_BUILD_ABSENT UINT64_MAX /* a d_len entry: this op is not run for this message */
+#define CAPNP_PACKED_MAX_BUILD_OPS 32u
+#define CAPNP_PACKED_MAX_BUILD_WORDS 64u     /* the root pointer word + the words of every struct */
+typedef struct capnp_packed_build_op {       /* 32 bytes, HOST memory, passed to the kernel by value */
+    uint32_t kind;       /* CAPNP_PACKED_FIELD_U8 .. LIST_64 as a WRITE, or CAPNP_PACKED_BUILD_STRUCT */
+    uint32_t target;     /* index of the BUILD_STRUCT op whose struct this op writes into
+                            (for BUILD_STRUCT: the parent); ignored for op 0 */
+    uint32_t offset;     /* data kinds: byte offset in target's data section;
+                            slice kinds and BUILD_STRUCT: pointer index in target */
+    uint32_t bit;        /* BOOL: 0-7; otherwise 0 */
+    uint16_t data_words, pointer_words; /* BUILD_STRUCT only */
+    uint32_t reserved[3]; /* 0 */
+} capnp_packed_build_op;
+int capnp_packed_build_fields_batch(const uint8_t* d_pool, uint64_t pool_len, uint32_t n,
+                                    const capnp_packed_build_op* ops /* HOST */, uint32_t n_ops,
+                                    const uint64_t* d_value /* n_ops * n */, const uint64_t* d_len /* n_ops * n */,
+                                    const uint64_t* d_count /* n_ops * n; may be NULL when no op is LIST_BIT */,
+                                    uint8_t* d_out /* NULL: sizes only */, const uint64_t* d_out_off,
+                                    const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                    void* stream);
 
 /* Exclusive scan of n lengths into n+1 offsets (d_off[0] = base, d_off[n] =
  * base + total), on device.

@@ -171,6 +171,28 @@ pub extern "capnp_packed" fn capnp_packed_gather_batch(
     d_in: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, n: u32,
     d_out: [*]u8, d_dst_off: [*]const u64, out_cap: u64, d_status: [*]i32, stream: ?*anyopaque,
 ) c_int;
+/// Struct building over a batch (struct capnp_packed_build_op): one fixed sequence of builder
+/// calls applied to n messages whose values come from op-major device columns; message i leaves
+/// as toBytes() at d_out + d_out_off[i]. `ops` is host memory (at most max_build_ops).
+pub const build_struct: u32 = 16;
+pub const build_absent: u64 = 0xFFFF_FFFF_FFFF_FFFF;
+pub const max_build_ops: u32 = 32;
+pub const max_build_words: u32 = 64;
+pub const BuildOp = extern struct {
+    kind: u32,
+    target: u32 = 0,
+    offset: u32 = 0,
+    bit: u32 = 0,
+    data_words: u16 = 0,
+    pointer_words: u16 = 0,
+    reserved: [3]u32 = .{ 0, 0, 0 },
+};
+pub extern "capnp_packed" fn capnp_packed_build_fields_batch(
+    d_pool: ?[*]const u8, pool_len: u64, n: u32, ops: [*]const BuildOp, n_ops: u32,
+    d_value: [*]const u64, d_len: [*]const u64, d_count: ?[*]const u64,
+    d_out: ?[*]u8, d_out_off: ?[*]const u64, d_out_cap: ?[*]const u64, d_out_len: [*]u64,
+    d_status: [*]i32, stream: ?*anyopaque,
+) c_int;
 /// Struct lists and pointer lists as element tables (struct capnp_packed_list_head): where one
 /// message's list lies and how many elements it has.
 pub const list_struct: u32 = 0;
